@@ -1,11 +1,23 @@
 """Benchmark: inner env-steps/s of fancy_ProMP/LongSimpleReacher-v0 black-box steps on MI355X.
 
 python bench.py [--gpus N] [--steps K] [--warmup W] [--global-envs G | --envs ENVS_PER_GPU]
+                [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up, W untimed steps, one
+untimed replay of the captured K-step graph (device warm), the K timed steps, the optional output
+dump, one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step and the run's
+shape).  --full adds the side measurements, each a run of its
+own: the CPU baseline (before the GPU is touched), the kernel-only graph and the return gather
+alone (the per-rank kernel / collective split), the roofline of the episode kernel, the basis
+GEMM as its own launch and, for N > 1, the weak-scaling point.
+--dump-outputs DIR writes what the last timed step returned (rank 0's shard: observations,
+final_observations, returns, terminated, truncated, trajectory_length, one DIR/<name>.npy each,
+float32 / float64).  The inputs are seeded, so the same arguments give the same files.
 
 BASELINE.json's metric is quoted at N = 65536 envs in total over 1/2/4/8 GPUs: the default is
 STRONG scaling (--global-envs 65536, each of the N ranks owns 65536/N envs).  --envs gives every
-rank a fixed number of envs instead (weak scaling).  With N > 1 the strong-scaling line also
-carries a weak-scaling measurement (65536 envs per GPU) as a secondary field.
+rank a fixed number of envs instead (weak scaling).  With N > 1 and --full the strong-scaling line
+also carries a weak-scaling measurement (65536 envs per GPU) as a secondary field.
 For N > 1, `bench.py --gpus N` starts the N ranks itself (torch.distributed.run as a child process,
 one process per GPU) unless a launcher already did (WORLD_SIZE set; it must equal --gpus); with
 fewer visible GPUs than ranks they share cuda:0 over gloo (rehearsal).  Env shards are independent
@@ -255,10 +267,12 @@ def _cpu_worker(args):
 
 
 # ----------------------------------------------------------------------------- GPU run
-def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev, overlap="auto"):
+def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev, overlap="auto", full=False):
     """K timed BB steps of this rank's shard (global envs [rank * n_local, (rank + 1) * n_local)),
     bracketed by barrier + synchronize on both sides.  Returns wall time (max over ranks), inner
-    steps (sum over ranks), this rank's event time per step, inner steps and the env."""
+    steps (sum over ranks), this rank's event time per step, inner steps, the env and the buffers
+    the last timed step wrote.  full: also time the return gather alone and the kernel-only graph
+    (runs of their own, before the timed steps); without it kern_ms is None."""
     import torch
 
     import fancy_gym_crowd_amd as fgx
@@ -291,11 +305,12 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
     rets = [ret, torch.empty_like(ret)] if can_overlap else [ret, ret]
     gbufs = [gbuf, torch.empty_like(gbuf)] if can_overlap else [gbuf, gbuf]
     comm = torch.cuda.Stream(device=dev) if can_overlap else None
-    st = {"k": 0, "gathers": 0, "free": [None, None], "pending": False}
+    st = {"k": 0, "gathers": 0, "free": [None, None], "pending": False, "last": 0}
 
     def bb_step(ov, count=True):
         s = st["k"] % 2 if ov else 0
         st["k"] += 1
+        st["last"] = s   # the return buffers this step writes
         if ov and st["free"][s] is not None:
             torch.cuda.current_stream().wait_event(st["free"][s])
         env.step_into(params, obs, rets[s], te, tr, tl, fobs, inner_steps=acc if count else None)
@@ -354,7 +369,7 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
 
     # the return gather alone (K captured all_gathers): the collective's own cost per BB step
     gather_ms = None
-    if gbuf is not None and gbuf.is_cuda and use_graph:
+    if full and gbuf is not None and gbuf.is_cuda and use_graph:
         cg, _ = capture(lambda: shard.gather_returns_into(gbuf, ret))
         if cg is not None:
             gather_ms = timed_graph(cg, None)
@@ -362,10 +377,12 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
 
     # kernel-only time: the K episode launches alone in a HIP graph, HIP events on the launch stream
     # (outside the timed region; it separates kernel time from the per-step collective)
-    kstep = lambda: env.step_into(params, obs, ret, te, tr, tl, fobs)   # noqa: E731
-    kgraph = capture(kstep)[0] if use_graph else None
-    kern_ms = timed_graph(kgraph, kstep)
-    del kgraph
+    kern_ms = None
+    if full:
+        kstep = lambda: env.step_into(params, obs, ret, te, tr, tl, fobs)   # noqa: E731
+        kgraph = capture(kstep)[0] if use_graph else None
+        kern_ms = timed_graph(kgraph, kstep)
+        del kgraph
 
     # the timed BB steps: K x (episode launch [+ return all_gather]).  RCCL collectives on device
     # buffers are captured into the same HIP graph as the kernels; the gloo rehearsal (host
@@ -381,7 +398,7 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
             if g is None:
                 gerr = e
                 continue
-            graphs[m] = (g, st["gathers"])
+            graphs[m] = (g, st["gathers"], st["last"])
         if len(graphs) == 2:   # one untimed replay of each, slowest rank decides, same pick everywhere
             t_in = timed_graph(graphs[False][0], None)
             t_ov = timed_graph(graphs[True][0], None)
@@ -392,12 +409,17 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
         elif graphs:
             ov = next(iter(graphs))
         if graphs:
-            graph, n_captured = graphs[ov]
+            graph, n_captured, last_captured = graphs[ov]
             graphs.clear()
         elif gerr:
             print(f"[bench] graph capture failed ({gerr}); timing eager launches", file=sys.stderr)
     if graph is None:
         n_captured = 0
+    elif not full and not trial:
+        # one untimed replay: the timed one then runs on a warm device (clocks up), as it does after
+        # --full's kernel-only graph or the schedule trial; without it 50 steps read 2-3% slower
+        graph.replay()
+        torch.cuda.synchronize()
     st["gathers"] = 0
     acc.zero_()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -408,7 +430,7 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
     ev0.record()
     if graph is not None:
         graph.replay()
-        st["gathers"] = n_captured
+        st["gathers"], st["last"] = n_captured, last_captured
     else:
         for _ in range(K):
             bb_step(ov)
@@ -423,9 +445,10 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
         dist.barrier()
         barrier_ms = (time.perf_counter() - tb) * 1e3
     inner_local = int(acc.sum().item())
-    coll_ms = max(0.0, step_ms - kern_ms) if dist is not None else 0.0
-    timing_local = [kern_ms, step_ms, coll_ms, barrier_ms, elapsed * 1e3, float(st["gathers"]),
-                    -1.0 if gather_ms is None else gather_ms]
+    # (-1 over the wire = not measured: the kernel-only graph and the lone gather are --full's)
+    coll_ms = 0.0 if dist is None else -1.0 if kern_ms is None else max(0.0, step_ms - kern_ms)
+    timing_local = [-1.0 if kern_ms is None else kern_ms, step_ms, coll_ms, barrier_ms, elapsed * 1e3,
+                    float(st["gathers"]), -1.0 if gather_ms is None else gather_ms]
     if dist is not None:
         elapsed = shard.max_over_ranks(elapsed, coll_dev)
         inner = shard.sum_over_ranks(inner_local, coll_dev)
@@ -435,8 +458,10 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
         inner = inner_local
         shards = [[lo, lo + N, inner_local]]
         timing = [timing_local]
-    per_rank = [{"rank": i, "kernel_ms_per_step": t[0], "step_ms": t[1], "exposed_collective_ms_per_step": t[2],
-                 "gather_ms": None if t[6] < 0 else t[6], "barrier_ms": t[3], "wall_ms": t[4], "gathers": int(t[5])}
+    opt = lambda x: None if x < 0 else x   # noqa: E731
+    per_rank = [{"rank": i, "kernel_ms_per_step": opt(t[0]), "step_ms": t[1],
+                 "exposed_collective_ms_per_step": opt(t[2]), "gather_ms": opt(t[6]), "barrier_ms": t[3],
+                 "wall_ms": t[4], "gathers": int(t[5])}
                 for i, t in enumerate(timing)]
     launch = "hip graph of the K steps" if graph is not None else "eager"
     if gbuf is not None:
@@ -445,7 +470,33 @@ def run_shard(env_id, n_local, rank, world, K, W, use_graph, dev, dist, coll_dev
         launch += (", captured)" if graph is not None else ")")
     return dict(elapsed=elapsed, inner=inner, inner_local=inner_local, kern_ms=kern_ms, env=env, params=params,
                 shards=shards, per_rank=per_rank, launch=launch, gathers=st["gathers"], capture_error=gerr,
-                schedule_trial=trial)
+                schedule_trial=trial,
+                # what a caller of the timed path holds after its last step (this rank's shard)
+                outputs={"observations": obs, "final_observations": fobs, "returns": rets[st["last"]],
+                         "terminated": te, "truncated": tr, "trajectory_length": tl})
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """Write the arrays of the last timed step as path/<name>.npy (floats keep their width, flags
+    and lengths as float32).  Past DUMP_BYTES_MAX in all, every array keeps the same fixed, seeded
+    sample of its rows (envs), in env order."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BYTES_MAX:
+        n = next(iter(arrs.values())).shape[0]
+        keep = max(1, int(DUMP_BYTES_MAX / (total / n + 8)))   # + 8: the row's index in sample_rows
+        rows = np.sort(np.random.default_rng(2024).choice(n, size=keep, replace=False))
+        arrs = {name: a[rows] for name, a in arrs.items()}
+        arrs["sample_rows"] = rows.astype(np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def roofline(env_id, env, N, kern_ms, inner_local, K, simds, build_id):
@@ -513,9 +564,14 @@ def main():
                     help="total envs over all ranks (strong scaling, the metric's definition)")
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (weak scaling instead)")
     ap.add_argument("--env-id", default=WORKLOAD)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: CPU baseline, kernel-only and gather-only timing, "
+                         "roofline, basis GEMM, weak-scaling point (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (rank 0's shard)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-weak", action="store_true", help="skip the secondary weak-scaling measurement")
+    ap.add_argument("--no-weak", action="store_true", help="--full without its weak-scaling measurement")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="launch the K steps eagerly instead of replaying them as one HIP graph")
     ap.add_argument("--overlap", choices=("auto", "on", "off"), default="auto",
@@ -537,7 +593,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # the CPU baseline runs first, before this process touches the GPU (its workers are forked)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)
 
     import torch
@@ -573,10 +629,13 @@ def main():
     else:
         n_local = args.envs
     K, W = args.steps, args.warmup
-    r = run_shard(args.env_id, n_local, rank, world, K, W, args.graph, dev, dist, coll_dev, args.overlap)
+    r = run_shard(args.env_id, n_local, rank, world, K, W, args.graph, dev, dist, coll_dev, args.overlap, args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["outputs"])
     weak = None
-    if strong and world > 1 and not args.no_weak:   # secondary: 65536 envs per GPU
-        w = run_shard(args.env_id, GLOBAL_ENVS, rank, world, K, W, args.graph, dev, dist, coll_dev, args.overlap)
+    if args.full and strong and world > 1 and not args.no_weak:   # secondary: 65536 envs per GPU
+        w = run_shard(args.env_id, GLOBAL_ENVS, rank, world, K, W, args.graph, dev, dist, coll_dev, args.overlap,
+                      args.full)
         weak = {"envs_per_gpu": GLOBAL_ENVS, "global_envs": GLOBAL_ENVS * world, "value": w["inner"] / w["elapsed"],
                 "ms_per_step": w["elapsed"] / K * 1e3, "kernel": w["env"].episode_kernel(),
                 "kernel_ms": w["kern_ms"]}
@@ -584,7 +643,9 @@ def main():
 
     if rank == 0:
         env = r["env"]
-        simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
+
+        def max_of(key):
+            return max((t[key] for t in r["per_rank"] if t[key] is not None), default=None)
         line = {
             "metric": METRIC,
             "value": r["inner"] / r["elapsed"],
@@ -592,6 +653,7 @@ def main():
             "n_gpus": world,
             "steps": K,
             "warmup": W,
+            "full": args.full,
             "ms_per_step": r["elapsed"] / K * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
@@ -613,24 +675,26 @@ def main():
             # the timed BB step (episode + return all_gather, HIP events), their difference = the
             # per-step collective, the closing barrier (host, outside the value window) and the
             # number of return gathers inside the timed region (= steps when N > 1)
-            "timing": {"kernel_ms_per_step_max": max(t["kernel_ms_per_step"] for t in r["per_rank"]),
-                       "step_ms_max": max(t["step_ms"] for t in r["per_rank"]),
-                       "exposed_collective_ms_per_step_max": max(t["exposed_collective_ms_per_step"]
-                                                                 for t in r["per_rank"]),
-                       "gather_ms_max": max((t["gather_ms"] for t in r["per_rank"] if t["gather_ms"] is not None),
-                                            default=None),
-                       "barrier_ms_max": max(t["barrier_ms"] for t in r["per_rank"]),
+            # (kernel, exposed collective and gather times are --full's: None in a plain run)
+            "timing": {"kernel_ms_per_step_max": max_of("kernel_ms_per_step"),
+                       "step_ms_max": max_of("step_ms"),
+                       "exposed_collective_ms_per_step_max": max_of("exposed_collective_ms_per_step"),
+                       "gather_ms_max": max_of("gather_ms"),
+                       "barrier_ms_max": max_of("barrier_ms"),
                        "gathers": r["gathers"],
                        "per_rank": r["per_rank"]},
-            "roofline": roofline(args.env_id, env, n_local, r["kern_ms"], r["inner_local"], K, simds, lib_build_id()),
         }
+        if args.full:
+            simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
+            line["roofline"] = roofline(args.env_id, env, n_local, r["kern_ms"], r["inner_local"], K, simds,
+                                        lib_build_id())
         if r["schedule_trial"]:
             line["timing"]["schedule_trial"] = r["schedule_trial"]
         if r["capture_error"]:
             line["timing"]["capture_error"] = r["capture_error"]
         if weak is not None:
             line["weak_scaling"] = weak
-        if world == 1 and env.T % 4 == 0:
+        if args.full and world == 1 and env.T % 4 == 0:
             try:
                 line["basis_gemm"] = basis_gemm(env, r["params"])
             except Exception as e:   # report, never fail the bench line on the side measurement

@@ -41,7 +41,7 @@ def test_bench_rccl_branch_one_rank():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "bench.py", "--force-dist", "--steps", "3", "--warmup", "1",
-                          "--global-envs", "8192", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True,
+                          "--global-envs", "8192", "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True,
                          text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

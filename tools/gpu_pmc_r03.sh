@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes for bench.py's roofline (profiles/pmc_summary.json via tools/pmc_summary.py): one
-# rocprofv3 --pmc pass per counter group over `bench.py --env-id ID --global-envs N` for every case
+# rocprofv3 --pmc pass per counter group over `bench.py --full --env-id ID --global-envs N` for every case
 # (the strong-scaling shard sizes of the metric, 65536 / G for G = 1, 2, 4, 8, config 3, and the
 # info_level=2 step of the metric env and of config 3); the
 # 65536-env metric run also carries the basis-GEMM launch (k_traj_mfma) for the MFMA counters.
@@ -18,7 +18,7 @@ for case in ${CASES:-65536:$METRIC 32768:$METRIC 16384:$METRIC 8192:$METRIC 6553
   echo "$env" > $d/workload.txt
   parts=${PARTS:-fetch write issue busy mix stall}
   [ "$tag" = "65536" ] && [ -z "$PARTS" ] && parts="$parts mfma"
-  cmd="bench.py --env-id $env --global-envs $n --steps 10 --warmup 2 --no-cpu-baseline"
+  cmd="bench.py --full --env-id $env --global-envs $n --steps 10 --warmup 2 --no-cpu-baseline"
   case $tag in
     *holelog) cmd="tools/bench_kernels.py loghole"; parts=${PARTS:-fetch write stall} ;;
     *log) cmd="tools/bench_kernels.py logsimple"; parts=${PARTS:-fetch write stall} ;;

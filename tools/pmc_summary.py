@@ -4,7 +4,7 @@
 
 Expects, per profiled case, a directory <src>/<case>/ holding `workload.txt` (the env id; default
 the metric's) and the sub-directories written by tools/gpu_pmc_r03.sh, one rocprofv3 pass each over
-`bench.py --env-id ID --global-envs ENVS --no-cpu-baseline`:
+`bench.py --full --env-id ID --global-envs ENVS --no-cpu-baseline`:
   fetch/  --pmc FETCH_SIZE
   write/  --pmc WRITE_SIZE
   issue/  --pmc SQ_WAVES SQ_INSTS_VALU GRBM_GUI_ACTIVE
