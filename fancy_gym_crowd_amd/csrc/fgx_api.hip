@@ -79,27 +79,30 @@ static const NlOps* nl_ops(int nl) {
   return nullptr;
 }
 
-// any per-step output, or the validity checks: the logging instantiations (fgx_dispatch.h)
-static bool episode_logs(const DevCfg& c, const Outputs& o) {
-  return o.positions || o.step_actions || o.step_obs || o.step_rewards || o.is_collided || o.end_effector ||
-         o.reward_dist || c.valid_flags != 0;
+// The episode kernel of this step (EK_*, fgx_select.h), decided here once: launch_episode passes the
+// id down to the unit that holds the kernel.  per_env_plans: the step runs on per-env (learned) plans
+static int select_kernel(const Handle& h, int mp, const Outputs& o, bool per_env_plans) {
+  return select_episode_kernel(
+      h.dc, SelectIn::from_outputs(h.dc, mp, o, per_env_plans, h.st.rew != nullptr, device_cus()),
+      KernelOverrides::from_env());
 }
 
-static int launch_episode(const Handle& h, int mp, const float* params, const float* dpos, const float* dvel,
-                          const Outputs& o, hipStream_t stream) {
-  if (const NlOps* ops = nl_ops(h.dc.nl)) return ops->episode(h.dc, h.st, mp, params, dpos, dvel, o, stream, g_err);
+static int launch_episode(const Handle& h, int mp, int kernel, const float* params, const float* dpos,
+                          const float* dvel, const Outputs& o, hipStream_t stream) {
+  // (the other link counts hold the logging k_episode only: EK_CLASSIC, anything else is refused there)
+  if (const NlOps* ops = nl_ops(h.dc.nl))
+    return ops->episode(h.dc, h.st, mp, kernel, params, dpos, dvel, o, stream, g_err);
   // HoleReacher up to info level 1: the producer / consumer pipeline (fgx_hp.h)
-  if (hp_applies(h.dc, h.st, mp, episode_logs(h.dc, o), o.positions || o.step_obs, h.st.plan_len != nullptr))
-    return fgx_launch_episode_hp(h.dc, h.st, mp, params, o, stream, g_err);
+  if (kernel == EK_HP) return fgx_launch_episode_hp(h.dc, h.st, mp, params, o, stream, g_err);
   const bool gen = mp != MP_GIVEN && h.dc.nb != 5;   // generic basis-count instantiations
   if (h.dc.env == ENV_SIMPLE)
-    return (gen ? fgx_launch_episode_simple_gen : fgx_launch_episode_simple)(h.dc, h.st, mp, params, dpos, dvel, o,
-                                                                           stream, g_err);
+    return (gen ? fgx_launch_episode_simple_gen : fgx_launch_episode_simple)(h.dc, h.st, mp, kernel, params, dpos,
+                                                                           dvel, o, stream, g_err);
   if (h.dc.env == ENV_HOLE)
-    return (gen ? fgx_launch_episode_hole_gen : fgx_launch_episode_hole)(h.dc, h.st, mp, params, dpos, dvel, o,
-                                                                       stream, g_err);
-  return (gen ? fgx_launch_episode_via_gen : fgx_launch_episode_via)(h.dc, h.st, mp, params, dpos, dvel, o, stream,
-                                                                     g_err);
+    return (gen ? fgx_launch_episode_hole_gen : fgx_launch_episode_hole)(h.dc, h.st, mp, kernel, params, dpos, dvel,
+                                                                       o, stream, g_err);
+  return (gen ? fgx_launch_episode_via_gen : fgx_launch_episode_via)(h.dc, h.st, mp, kernel, params, dpos, dvel, o,
+                                                                     stream, g_err);
 }
 
 static int launch_reset(const Handle& h, const uint64_t* seeds, const uint8_t* mask, int rs_mode, float* obs,
@@ -591,9 +594,8 @@ static bool info_too_large(const Handle* h, const fgx_info* info) {
 // k_episode_v2 needs none).  A first such step inside a HIP graph capture is refused rather than
 // allocating there (hipMalloc would invalidate the capture): run it once before capturing.  Per-step
 // observations on one handle must stay on one stream (the scratch is per handle).
-static int attach_obs_scratch(Handle* h, Outputs& o, int mp, hipStream_t stream) {
-  if (!o.step_obs || h->dc.env != ENV_SIMPLE) return FGX_OK;
-  if (episode_kernel_choice(h->dc, mp, true, h->learned()) == EK_V2) return FGX_OK;
+static int attach_obs_scratch(Handle* h, Outputs& o, int kernel, hipStream_t stream) {
+  if (!o.step_obs || h->dc.env != ENV_SIMPLE || kernel == EK_V2) return FGX_OK;
   const size_t nq = (size_t)h->dc.T * h->dc.nl * h->dc.N;
   if (!h->obs_scratch) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -625,7 +627,12 @@ int fgx_step(void* handle, const float* params, float* obs, double* ret, uint8_t
     return fail(FGX_E_INVALID, "reward_dist and reward_ctrl must be given together");
   if (info_too_large(h, info)) return fail(FGX_E_UNSUPPORTED, "per-step info arrays need n_envs < 2^24");
   Outputs o = make_outputs(obs, ret, terminated, truncated, traj_len, final_obs, info, autoreset);
-  if (const int rc = attach_obs_scratch(h, o, h->learned() ? MP_GIVEN : h->dc.mp, (hipStream_t)stream)) return rc;
+  if (h->learned()) {   // k_traj_env writes the planned positions / velocities, not the episode kernel
+    o.positions = nullptr;
+    o.velocities = nullptr;
+  }
+  const int kernel = select_kernel(*h, h->learned() ? MP_GIVEN : h->dc.mp, o, h->learned());
+  if (const int rc = attach_obs_scratch(h, o, kernel, (hipStream_t)stream)) return rc;
   if (h->learned()) {
     // per-env plans first (and, when requested, the time-major info copies), then the episode
     // over the given plans with per-env lengths
@@ -636,12 +643,10 @@ int fgx_step(void* handle, const float* params, float* obs, double* ret, uint8_t
     if (rc) return rc;
     Handle hh = *h;
     hh.st.plan_len = h->plan_len;
-    o.positions = nullptr;
-    o.velocities = nullptr;
     // (params only for the validity checks of the raw tau / delay entries)
-    return launch_episode(hh, MP_GIVEN, params, P, V, o, (hipStream_t)stream);
+    return launch_episode(hh, MP_GIVEN, kernel, params, P, V, o, (hipStream_t)stream);
   }
-  return launch_episode(*h, h->dc.mp, params, nullptr, nullptr, o, (hipStream_t)stream);
+  return launch_episode(*h, h->dc.mp, kernel, params, nullptr, nullptr, o, (hipStream_t)stream);
 }
 
 int fgx_step_traj(void* handle, const float* des_pos, const float* des_vel, float* obs, double* ret,
@@ -658,10 +663,11 @@ int fgx_step_traj(void* handle, const float* des_pos, const float* des_vel, floa
     return fail(FGX_E_INVALID, "reward_dist and reward_ctrl must be given together");
   if (info_too_large(h, info)) return fail(FGX_E_UNSUPPORTED, "per-step info arrays need n_envs < 2^24");
   Outputs o = make_outputs(obs, ret, terminated, truncated, traj_len, final_obs, info, autoreset);
-  if (const int rc = attach_obs_scratch(h, o, MP_GIVEN, (hipStream_t)stream)) return rc;
   o.positions = nullptr;
   o.velocities = nullptr;   // the caller already holds the desired trajectories
-  return launch_episode(*h, MP_GIVEN, nullptr, des_pos, des_vel, o, (hipStream_t)stream);
+  const int kernel = select_kernel(*h, MP_GIVEN, o, false);
+  if (const int rc = attach_obs_scratch(h, o, kernel, (hipStream_t)stream)) return rc;
+  return launch_episode(*h, MP_GIVEN, kernel, nullptr, des_pos, des_vel, o, (hipStream_t)stream);
 }
 
 int fgx_trajectory(void* handle, const float* params, float* des_pos, float* des_vel, void* stream) {
@@ -730,12 +736,11 @@ int fgx_get_tables(void* handle, float* out, void* stream) {
 int fgx_episode_kernel(void* handle, int32_t info_level) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(FGX_E_INVALID, "null handle");
-  const int mp = h->learned() ? MP_GIVEN : h->dc.mp;
-  // the predicate launch_episode_nl uses: any per-step output, or the validity checks
-  const bool log = info_level >= 1 || h->dc.valid_flags != 0;
-  if (h->dc.nl == 2 || h->dc.nl == 5)
-    if (hp_applies(h->dc, h->st, mp, log, info_level >= 2, h->learned())) return EK_HP;
-  return episode_kernel_choice(h->dc, mp, log, h->learned());
+  // the function fgx_step launches by (select_kernel), asked with the info level in place of the outputs
+  return select_episode_kernel(h->dc,
+                               SelectIn::from_info_level(h->dc, h->learned() ? MP_GIVEN : h->dc.mp, info_level,
+                                                         h->learned(), h->st.rew != nullptr, device_cus()),
+                               KernelOverrides::from_env());
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <string>
 #include <unordered_map>
 
 #include "fgx_rng.h"
@@ -39,6 +40,26 @@ inline hipError_t raise_lds_limit(const void* kernel, size_t lds) {
   const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e == hipSuccess) have = lds;
   return e;
+}
+
+// Host: the current device's CU count (256 if it cannot be asked)
+inline int device_cus() {
+  static const int n = [] {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      cus = 256;
+    return cus;
+  }();
+  return n;
+}
+
+// Host: the status of the launch just made: 0, or -2 with "<what>: <HIP's message>" in err
+inline int launch_status(const char* what, std::string& err) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  err = std::string(what) + ": " + hipGetErrorString(e);
+  return -2;
 }
 
 constexpr int kMaxLinks = 8;

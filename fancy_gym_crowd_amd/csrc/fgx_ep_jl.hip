@@ -8,21 +8,10 @@
 #include <cstdlib>
 
 namespace {
-int jl_cus() {
-  static const int n = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
-
-template <int MP, int NL, int NB, int HLP = 0>
+template <int MP, int NL, int NB>
 int launch_jl(const fgx::DevCfg& c, const fgx::DevState& s, const float* params, const fgx::Outputs& o,
               hipStream_t stream, std::string& err) {
-  using S = fgx::JlShape<NL, HLP>;
+  using S = fgx::JlShape<NL>;
   if constexpr (NB != 0) {
     if (c.stride != fgx::Traj<MP, 1, NB>::KS) {
       err = "basis table stride does not match the compiled layout";
@@ -36,45 +25,23 @@ int launch_jl(const fgx::DevCfg& c, const fgx::DevState& s, const float* params,
   // the reset wave (fgx_jl.h) while every workgroup has a CU of its own (the 8-GPU shard: 8192 envs
   // 23.8-24.0 -> 21.9-22.2 us, config 2 22.4 -> 20.1 us); past that its fifth wave costs a workgroup
   // slot per CU (32768 envs 45.2 -> 48.2 us, profiles/r06_jl_resetwave_ab.log).  FGX_JL_RW=0 / 1: A/B
-  int rw = (!HLP && blocks <= (unsigned)jl_cus()) ? 1 : 0;
-  if (const char* v = std::getenv("FGX_JL_RW")) rw = (!HLP && v[0] == '1') ? 1 : 0;
-  hipLaunchKernelGGL((fgx::k_episode_jl<MP, NL, NB, HLP>), dim3(blocks), dim3(S::THREADS + 64 * rw), S::lds_bytes(),
+  int rw = blocks <= (unsigned)fgx::device_cus() ? 1 : 0;
+  if (const char* v = std::getenv("FGX_JL_RW")) rw = v[0] == '1' ? 1 : 0;
+  hipLaunchKernelGGL((fgx::k_episode_jl<MP, NL, NB>), dim3(blocks), dim3(S::THREADS + 64 * rw), S::lds_bytes(),
                      stream, c, s, params, o, gw, rw);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { err = std::string("k_episode_jl launch: ") + hipGetErrorString(e); return -2; }
-  return 0;
-}
-
-// the helper form (fgx_jl.h, HLP 1 / 2): ProMP on the column table, measured slower than the plain
-// form and compiled only into diagnostics builds (-DFGX_JL_HELPER_FORM,
-// _build.build_variant); FGX_JL_HELPER=1 / 2 selects it there and is refused by the release build
-inline int jl_helper(const fgx::DevCfg& c) {
-  if (const char* v = std::getenv("FGX_JL_HELPER")) return v[0] == '1' ? 1 : v[0] == '2' ? 2 : 0;
-  (void)c;
-  return 0;
+  return fgx::launch_status("k_episode_jl launch", err);
 }
 
 template <int MP, int NB>
 int launch_jl_nl(const fgx::DevCfg& c, const fgx::DevState& s, const float* params, const fgx::Outputs& o,
                  hipStream_t stream, std::string& err) {
-  if (const int h = jl_helper(c)) {
-#ifdef FGX_JL_HELPER_FORM
-    if constexpr (MP == fgx::MP_PROMP && NB == 5) {
-      if (h == 1) {
-        if (c.nl == 2) return launch_jl<MP, 2, NB, 1>(c, s, params, o, stream, err);
-        if (c.nl == 5) return launch_jl<MP, 5, NB, 1>(c, s, params, o, stream, err);
-      } else {
-        if (c.nl == 2) return launch_jl<MP, 2, NB, 2>(c, s, params, o, stream, err);
-        if (c.nl == 5) return launch_jl<MP, 5, NB, 2>(c, s, params, o, stream, err);
-      }
+  // the helper form (a joint wave and a helper wave per workgroup, FGX_JL_HELPER=1 / 2) measured slower
+  // at every shard size and was removed: asking for it is an error, not the plain form
+  if (const char* v = std::getenv("FGX_JL_HELPER"))
+    if (v[0] == '1' || v[0] == '2') {
+      err = "k_episode_jl: FGX_JL_HELPER asks for the helper form, which was removed (DESIGN.md 4.6a)";
+      return -4;
     }
-#else
-    (void)h;
-    err = "k_episode_jl: FGX_JL_HELPER asks for the helper form, which this build does not contain "
-          "(a diagnostics build with -DFGX_JL_HELPER_FORM does)";
-    return -4;
-#endif
-  }
   if (c.nl == 2) return launch_jl<MP, 2, NB>(c, s, params, o, stream, err);
   if (c.nl == 5) return launch_jl<MP, 5, NB>(c, s, params, o, stream, err);
   err = "k_episode_jl: n_links not instantiated (supported: 2, 5)";

@@ -19,19 +19,12 @@ namespace {
 using namespace fgx;
 constexpr int NLV = FGX_NL;
 
-int hip_status(const char* what, std::string& err) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  err = std::string(what) + ": " + hipGetErrorString(e);
-  return -2;
-}
-
-int nl_episode(const DevCfg& c, const DevState& s, int mp, const float* params, const float* dpos, const float* dvel,
-               const Outputs& o, hipStream_t stream, std::string& err) {
+int nl_episode(const DevCfg& c, const DevState& s, int mp, int kernel, const float* params, const float* dpos,
+               const float* dvel, const Outputs& o, hipStream_t stream, std::string& err) {
   switch (c.env) {
-    case ENV_SIMPLE: return launch_episode_env<ENV_SIMPLE, 0, NLV>(c, s, mp, params, dpos, dvel, o, stream, err);
-    case ENV_HOLE: return launch_episode_env<ENV_HOLE, 0, NLV>(c, s, mp, params, dpos, dvel, o, stream, err);
-    case ENV_VIA: return launch_episode_env<ENV_VIA, 0, NLV>(c, s, mp, params, dpos, dvel, o, stream, err);
+    case ENV_SIMPLE: return launch_episode_env<ENV_SIMPLE, 0, NLV>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
+    case ENV_HOLE: return launch_episode_env<ENV_HOLE, 0, NLV>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
+    case ENV_VIA: return launch_episode_env<ENV_VIA, 0, NLV>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
   }
   err = "bad env kind";
   return -1;
@@ -42,7 +35,7 @@ int nl_reset(const DevCfg& c, const DevState& s, const uint64_t* seeds, const ui
   const int threads = 256;
   hipLaunchKernelGGL((k_reset<NLV>), dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s,
                      seeds, mask, rs_mode, obs);
-  return hip_status("k_reset", err);
+  return launch_status("k_reset", err);
 }
 
 int nl_step_raw(const DevCfg& c, const DevState& s, const float* act, float* obs, double* rew, uint8_t* term,
@@ -57,21 +50,21 @@ int nl_step_raw(const DevCfg& c, const DevState& s, const float* act, float* obs
   else
     hipLaunchKernelGGL((k_step_raw<ENV_VIA, NLV>), grid, block, lds, stream, c, s, act, obs, rew, term, trunc,
                        final_obs, autoreset);
-  return hip_status("k_step_raw", err);
+  return launch_status("k_step_raw", err);
 }
 
 int nl_traj(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel, hipStream_t stream,
             std::string& err) {
   const int rr = launch_traj_run<NLV>(c, s, params, dpos, dvel, stream);
   if (rr == 0) return 0;
-  if (rr == 2) return hip_status("k_traj_run", err);
+  if (rr == 2) return launch_status("k_traj_run", err);
   const int threads = 256;
   const dim3 grid((unsigned)((c.N + threads - 1) / threads)), block(threads);
   if (c.mp == MP_PROMP) hipLaunchKernelGGL((k_traj_valu<MP_PROMP, NLV, 0>), grid, block, 0, stream, c, s, params, dpos, dvel);
   else if (c.mp == MP_DMP) hipLaunchKernelGGL((k_traj_valu<MP_DMP, NLV, 0>), grid, block, 0, stream, c, s, params, dpos, dvel);
   else if (c.mp == MP_PRODMP) hipLaunchKernelGGL((k_traj_valu<MP_PRODMP, NLV, 0>), grid, block, 0, stream, c, s, params, dpos, dvel);
   else { err = "step-based handle has no trajectory generator"; return -1; }
-  return hip_status("k_traj_valu", err);
+  return launch_status("k_traj_valu", err);
 }
 
 int nl_traj_env(const DevCfg& c, const DevState& s, const float* params, float* env_tab, float* dpos, float* dvel,
@@ -86,7 +79,7 @@ int nl_traj_env(const DevCfg& c, const DevState& s, const float* params, float* 
   else if (c.mp == MP_PRODMP) FGX_NL_TRAJ_ENV(MP_PRODMP);
   else { err = "learned phase parameters need a movement primitive"; return -1; }
 #undef FGX_NL_TRAJ_ENV
-  return hip_status("k_traj_env", err);
+  return launch_status("k_traj_env", err);
 }
 }  // namespace
 

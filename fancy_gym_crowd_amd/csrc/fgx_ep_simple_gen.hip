@@ -1,8 +1,8 @@
 // SimpleReacher (torque) instantiations of k_episode, NB = 0 (generic runtime basis count).
 #include "fgx_dispatch.h"
 
-int fgx_launch_episode_simple_gen(const fgx::DevCfg& c, const fgx::DevState& s, int mp, const float* params,
+int fgx_launch_episode_simple_gen(const fgx::DevCfg& c, const fgx::DevState& s, int mp, int kernel, const float* params,
                                   const float* dpos, const float* dvel, const fgx::Outputs& o, hipStream_t stream,
                                   std::string& err) {
-  return fgx::launch_episode_env<fgx::ENV_SIMPLE, 0>(c, s, mp, params, dpos, dvel, o, stream, err);
+  return fgx::launch_episode_env<fgx::ENV_SIMPLE, 0>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
 }

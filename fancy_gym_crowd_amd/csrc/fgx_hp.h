@@ -31,21 +31,18 @@
 // One LDS-only barrier per two-sample chunk.  The producer reads the basis rows from global memory
 // (all lanes the same row: one broadcast request per wave), so LDS holds only the rings.
 //
-// Served (hp_applies): HoleReacher with the simple reward function, 5 links, 5 basis functions per
-// joint, shared tables (no learned tau / delay), static replanning schedules, no
+// Served (select_episode_kernel, fgx_select.h): HoleReacher with the simple reward function, 5 links,
+// 5 basis functions per joint, shared tables (no learned tau / delay), static replanning schedules, no
 // condition_on_desired, no validity checks, max_episode_steps <= 200; with per-step info arrays
 // (info_level 1 / 2, a reward_aggregation reading step_rewards) the INFO instantiation.  Every output,
 // every per-step array and the whole env state equal k_episode's bit for bit (tests/test_gpu_hp.py).
 #pragma once
-#include <cstdlib>
-#include <cstring>
 #include <string>
 
 #include "fgx_v2.h"
 
 namespace fgx {
 
-constexpr int EK_HP = 8;   // fgx_episode_kernel's id (include/fgx.h)
 constexpr int kHpNS = 5;   // second-half starts s = 64, 72, ..., 96 of numpy's split for L in (128, 200]
 constexpr int kHpS0 = 64;
 constexpr int kHpNR = 2;   // of them in the producer's registers (64, 72); the rest in LDS
@@ -141,7 +138,7 @@ __global__ __launch_bounds__(192 * G) void k_episode_hp(DevCfg c, DevState s, co
   const bool valid = e0 < N;
   const int64_t e = valid ? e0 : N - 1;   // clamped: loads stay in bounds, nothing is stored
   const int T = c.T;
-  double* cand = s.rew;   // candidate final states [ci][q | q̇ | |ee - goal|^2][N] (the handle's direct-env scratch)
+  double* cand = s.rew;   // candidate final states [ci][q | q̇][N] (the handle's direct-env scratch)
   constexpr int CR = hp_cand_rows<NL>();
 
   // ---- every role: the env's static segment end (black_box_wrapper.py:233-239: plan end, TimeLimit,
@@ -621,30 +618,6 @@ inline size_t hp_lds_bytes(int nl, int groups) {
   return (size_t)groups * (nl == 5 ? HpLayout<5>::GROUP : HpLayout<2>::GROUP) * sizeof(double);
 }
 static_assert(4 * HpLayout<5>::GROUP * sizeof(double) <= 160 * 1024, "k_episode_hp: four groups fit one CU's LDS");
-
-// k_episode_hp serves this step (FGX_HP=0 or any FGX_EPISODE_KERNEL but "hp" keep the others: A/B, tests)
-// log: some per-step array is written (the INFO instantiation; FGX_V2=0 keeps the logging k_episode)
-// heavy: the verbose-2 rows (planned positions / velocities, step observations): k_episode_v2h stays
-// faster there (65536 envs: 1026 vs 1637 us, profiles/r05_s9_jlhelper_traj_hpinfo.jsonl), so k_episode_hp takes
-// them only when forced (FGX_HP=1); FGX_HP=0 never takes it
-inline bool hp_applies(const DevCfg& c, const DevState& s, int mp, bool log, bool heavy, bool per_env_plans) {
-  bool force = false;
-  if (const char* v = std::getenv("FGX_HP")) {
-    if (std::strcmp(v, "0") == 0) return false;
-    force = std::strcmp(v, "1") == 0;
-  }
-  if (heavy && !force) return false;
-  // a forced kernel wins (fgx_dispatch.h): any FGX_EPISODE_KERNEL other than "hp" keeps k_episode_hp out
-  if (const char* v = std::getenv("FGX_EPISODE_KERNEL"))
-    if (*v && std::strcmp(v, "hp") != 0) return false;
-  if (log)
-    if (const char* v = std::getenv("FGX_V2"))
-      if (std::strcmp(v, "0") == 0) return false;
-  return c.env == ENV_HOLE && c.rew_fct == REW_SIMPLE && c.nl == 5 && c.nb == 5 &&
-         (mp == MP_PROMP || mp == MP_DMP || mp == MP_PRODMP) && !per_env_plans && !c.learn_tau && !c.learn_delay &&
-         !c.sched_state && !c.cond_desired && c.valid_flags == 0 && c.max_steps <= 200 && c.T <= 256 &&
-         s.rew != nullptr;
-}
 
 }  // namespace fgx
 

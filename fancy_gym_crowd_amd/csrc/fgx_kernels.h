@@ -1297,7 +1297,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // same fgx_sincos on the same q; q[0]'s are FK's, computed for the dynamics anyway).  Two staging
 // slots per dynamics wave, one LDS-only barrier per sample (s_barrier after lgkmcnt(0): a
 // __syncthreads fence would make the storing waves wait for their own stores every sample).  The
-// grid covers N with whole workgroups (N % 256 == 0, fgx_dispatch.h): every wave meets every barrier.
+// grid covers N with whole workgroups (N % 256 == 0, fgx_select.h): every wave meets every barrier.
 template <int ENV, int MP, int CTRL, int NL, int NB>
 __global__ __launch_bounds__(512) void k_episode_v2h(DevCfg c, DevState s, const float* __restrict__ params,
                                                      const float* __restrict__ dpos, const float* __restrict__ dvel,

@@ -26,7 +26,7 @@
 //
 // Every value equals the logging k_episode's (+ k_info_obs): bit-identical results
 // (tests/test_gpu_info_rows.py).  Served: ENV_SIMPLE + PD + shared tables, static replanning
-// schedules, max_episode_steps <= 200, no validity checks (fgx_dispatch.h).
+// schedules, max_episode_steps <= 200, no validity checks (fgx_select.h).
 #pragma once
 #include "fgx_jp.h"
 

@@ -17,7 +17,7 @@
 //
 // Every expression rounds exactly as in k_episode (same operations, same order), so results are
 // bit-identical (tests/test_gpu_ws.py).  Served: ENV_SIMPLE + PD + shared tables + info_level < 2
-// + static replanning schedules + T <= 256 (fgx_dispatch.h picks among k_episode / _jp / _ws).
+// + static replanning schedules + T <= 256 (fgx_select.h picks among k_episode / _jp / _ws).
 #pragma once
 #include "fgx_jp.h"
 

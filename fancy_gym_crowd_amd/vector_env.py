@@ -382,7 +382,10 @@ class BlackBoxVectorEnv:
         (HoleReacher up to info_level 1); all nine produce bit-identical results.  Whenever some per-step
         array is written (info_level >= 1, or a reward_aggregation that reads step_rewards) the launch
         takes k_episode_hp (HoleReacher below the verbose-2 rows), k_episode_v2 (SimpleReacher + PD),
-        k_episode_v2h (the direct envs at a multiple of 256 envs) or the logging k_episode."""
+        k_episode_v2h (the direct envs at a multiple of 256 envs) or the logging k_episode.  The name
+        comes from the function the launch itself decides by (csrc/fgx_select.h: select_episode_kernel,
+        asked with this info level in place of the output pointers), FGX_EPISODE_KERNEL / FGX_V2 /
+        FGX_HP as set at the time of the call included."""
         lvl = self.info_level if info_level is None else int(info_level)
         if self._needs_step_rewards():
             lvl = max(lvl, 1)

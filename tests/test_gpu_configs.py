@@ -6,7 +6,7 @@ oracle env seeded with its GLOBAL index as the device env was (reset(seed=0) -> 
 flags and trajectory lengths bit-exact, returns within 16 ulp, observations within 1e-5.  Config 3
 (HoleReacher, collisions end episodes early) additionally compares the flags and lengths of the
 FULL batch against the oracle, run in worker processes.  Each test also asserts which episode
-kernel fgx_dispatch.h:episode_kernel_choice picks at that size (env.episode_kernel()).
+kernel fgx_select.h:select_episode_kernel picks at that size (env.episode_kernel()).
 """
 import concurrent.futures as cf
 import multiprocessing as mproc

@@ -199,9 +199,9 @@ def test_hp_info_reward_aggregation(monkeypatch):
 
 
 def test_hp_fast_fk_near_thresholds(monkeypatch):
-    """info_level 0 takes the collision booleans from an error-bounded approximate FK and recomputes a
-    lane exactly where a decision is within its bound (fgx_hp.h: hp_fast_collision, hp_link_wall_rb).
-    Zero-velocity plans (ProMP, velocity controller, zero weights) hold each env at a pose built to sit
+    """A near-threshold bit-identity test of k_episode_hp's consumers, whose FK and collision tests are
+    the exact ones (Env::fk's operations, fgx_hp.h): poses whose collision decisions sit on their
+    thresholds must come out as k_episode's.  Zero-velocity plans (ProMP, velocity controller, zero weights) hold each env at a pose built to sit
     on a decision's threshold for the whole segment: arms lying within 1e-17 .. 1e-12 of the ground
     (the wall test's skip rule and its end-point comparisons), links folded back to within 1e-13 ..
     1e-11 rad (ccw values around the self-collision test's 1e-12), the collinear reset pose, squares

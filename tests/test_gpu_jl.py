@@ -167,9 +167,9 @@ def test_jl_equals_classic_split_autoreset(N, rw, monkeypatch):
 
 
 def test_jl_helper_form_not_in_release_build(monkeypatch):
-    """k_episode_jl's helper form (fgx_jl.h HLP; measured slower) is compiled only into
-    diagnostics builds (-DFGX_JL_HELPER_FORM): asking the release library for it is an error, not a
-    silent fallback to the plain kernel."""
+    """k_episode_jl's helper form (FGX_JL_HELPER=1|2; measured slower and removed from the sources,
+    DESIGN.md 4.6a) is in no build: asking the library for it is an error, not a silent fallback to
+    the plain kernel."""
     monkeypatch.setenv("FGX_JL_HELPER", "1")
     monkeypatch.setenv("FGX_EPISODE_KERNEL", "jl")
     env = fgx.make("fancy_ProMP/LongSimpleReacher-v0", num_envs=64, device=DEV, info_level=0)

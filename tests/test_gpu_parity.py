@@ -24,7 +24,7 @@ def np_(t):
 
 
 def kernel_is(got, want):
-    """episode kernel name check (env.episode_kernel(), fgx_dispatch.h)"""
+    """episode kernel name check (env.episode_kernel(), fgx_select.h)"""
     return got == want
 
 

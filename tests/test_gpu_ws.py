@@ -52,7 +52,7 @@ def test_ws_equals_classic_nan_and_restored_steps():
 
 
 def test_episode_kernel_selection():
-    """fgx_episode_kernel reports the measured choice (fgx_dispatch.h episode_kernel_choice)."""
+    """fgx_episode_kernel reports the measured choice (fgx_select.h select_episode_kernel)."""
     rp = {"black_box_kwargs": {"replanning_schedule": fgx.ReplanEvery(25)}}
     cases = [("fancy_ProMP/LongSimpleReacher-v0", None, 65536, 0, "k_episode"),      # the metric config
              ("fancy_ProMP/LongSimpleReacher-v0", None, 65536, 2, "k_episode_v2"),   # per-step info arrays

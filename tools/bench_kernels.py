@@ -229,15 +229,6 @@ if __name__ == "__main__":
                 episode("fancy_ProDMP/HoleReacher-v0", n, label=f"config3 {label}", reps=5)
         for k in ("FGX_HP_G", "FGX_EPISODE_KERNEL"):
             os.environ.pop(k, None)
-    if "jlh" in which:   # the 8-GPU shard sizes: k_episode_jl vs its helper form, alternated three times
-        for _ in range(3):
-            for n in (8192, 16384, 32768):
-                for h in ("0", "1", "2"):
-                    os.environ["FGX_EPISODE_KERNEL"] = "jl"
-                    os.environ["FGX_JL_HELPER"] = h
-                    episode("fancy_ProMP/LongSimpleReacher-v0", n, label=f"metric jl helper={h}")
-        for k in ("FGX_EPISODE_KERNEL", "FGX_JL_HELPER"):
-            os.environ.pop(k, None)
     if "hpinfo" in which:   # config 3's verbose-2 / info-level-1 public step(): k_episode_hp vs v2h vs logging
         import os
         for lvl in (2, 1):
