@@ -11,13 +11,11 @@
 #include <string>
 
 #include "../../include/fgx.h"
-#include "fgx_kernels.h"
-#include "fgx_tables_k.h"
 #include "fgx_aux.h"
-#include "fgx_dispatch.h"
-#include "fgx_learned.h"
-#include "fgx_step.h"
-#include "fgx_hp.h"
+#include "fgx_kernels.h"
+#include "fgx_launch.h"
+#include "fgx_select.h"
+#include "fgx_tables_k.h"
 
 using namespace fgx;
 
@@ -62,87 +60,21 @@ size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 }  // namespace
 
 // ------------------------------------------------------------------------ dispatch
-// The episode kernels are instantiated per env kind in their own translation units
-// (fgx_ep_<env>.hip, fgx_ep_<env>_gen.hip) so that the build compiles them in parallel.
-#define FGX_FOR_NL(X) X(2) X(5)
-
-// the kernel families of the other link counts (fgx_ep_nl.h); null for 2 and 5
-static const NlOps* nl_ops(int nl) {
-  switch (nl) {
-    case 1: return fgx_nl_ops_1();
-    case 3: return fgx_nl_ops_3();
-    case 4: return fgx_nl_ops_4();
-    case 6: return fgx_nl_ops_6();
-    case 7: return fgx_nl_ops_7();
-    case 8: return fgx_nl_ops_8();
-  }
-  return nullptr;
+// Every kernel but the table, state and self-test kernels of this unit is launched through the
+// table of the handle's link count (NlOps, fgx_launch.h; one translation unit per count, fgx_ep_nl.h).
+// build_devcfg admits 1..kMaxLinks only, so a handle always has one.
+static const NlOps& nl_ops(int nl) {
+  static const NlOps* const ops[kMaxLinks] = {fgx_nl_ops_1(), fgx_nl_ops_2(), fgx_nl_ops_3(), fgx_nl_ops_4(),
+                                              fgx_nl_ops_5(), fgx_nl_ops_6(), fgx_nl_ops_7(), fgx_nl_ops_8()};
+  return *ops[nl - 1];
 }
 
-// The episode kernel of this step (EK_*, fgx_select.h), decided here once: launch_episode passes the
-// id down to the unit that holds the kernel.  per_env_plans: the step runs on per-env (learned) plans
+// The episode kernel of this step (EK_*, fgx_select.h), decided here once: the table's episode entry
+// passes the id down to the unit that holds the kernel.  per_env_plans: the step runs on per-env (learned) plans
 static int select_kernel(const Handle& h, int mp, const Outputs& o, bool per_env_plans) {
   return select_episode_kernel(
       h.dc, SelectIn::from_outputs(h.dc, mp, o, per_env_plans, h.st.rew != nullptr, device_cus()),
       KernelOverrides::from_env());
-}
-
-static int launch_episode(const Handle& h, int mp, int kernel, const float* params, const float* dpos,
-                          const float* dvel, const Outputs& o, hipStream_t stream) {
-  // (the other link counts hold the logging k_episode only: EK_CLASSIC, anything else is refused there)
-  if (const NlOps* ops = nl_ops(h.dc.nl))
-    return ops->episode(h.dc, h.st, mp, kernel, params, dpos, dvel, o, stream, g_err);
-  // HoleReacher up to info level 1: the producer / consumer pipeline (fgx_hp.h)
-  if (kernel == EK_HP) return fgx_launch_episode_hp(h.dc, h.st, mp, params, o, stream, g_err);
-  const bool gen = mp != MP_GIVEN && h.dc.nb != 5;   // generic basis-count instantiations
-  if (h.dc.env == ENV_SIMPLE)
-    return (gen ? fgx_launch_episode_simple_gen : fgx_launch_episode_simple)(h.dc, h.st, mp, kernel, params, dpos,
-                                                                           dvel, o, stream, g_err);
-  if (h.dc.env == ENV_HOLE)
-    return (gen ? fgx_launch_episode_hole_gen : fgx_launch_episode_hole)(h.dc, h.st, mp, kernel, params, dpos, dvel,
-                                                                       o, stream, g_err);
-  return (gen ? fgx_launch_episode_via_gen : fgx_launch_episode_via)(h.dc, h.st, mp, kernel, params, dpos, dvel, o,
-                                                                     stream, g_err);
-}
-
-static int launch_reset(const Handle& h, const uint64_t* seeds, const uint8_t* mask, int rs_mode, float* obs,
-                        hipStream_t stream) {
-  const int threads = 256;
-  const int blocks = (int)((h.dc.N + threads - 1) / threads);
-#define X(NL)                                                                                                    \
-  if (h.dc.nl == NL) {                                                                                           \
-    hipLaunchKernelGGL((k_reset<NL>), dim3(blocks), dim3(threads), 0, stream, h.dc, h.st, seeds, mask, rs_mode, obs); \
-    HIP_TRY(hipGetLastError());                                                                           \
-    return FGX_OK;                                                                                        \
-  }
-  FGX_FOR_NL(X)
-#undef X
-  if (const NlOps* ops = nl_ops(h.dc.nl)) return ops->reset(h.dc, h.st, seeds, mask, rs_mode, obs, stream, g_err);
-  return fail(FGX_E_UNSUPPORTED, "n_links must be in 1..8");
-}
-
-static int launch_traj_env(const Handle& h, const float* params, float* pos, float* vel, hipStream_t stream,
-                           float* info_pos = nullptr, float* info_vel = nullptr) {
-  const int threads = 256;
-  const int blocks = (int)((h.dc.N + threads - 1) / threads);
-#define LAUNCH1(MPV, NLV, NBV)                                                                           \
-  hipLaunchKernelGGL((k_traj_env<MPV, NLV, NBV>), dim3(blocks), dim3(threads), 0, stream, h.dc, h.st, params, \
-                     h.env_tab, pos, vel, h.plan_len, info_pos, info_vel)
-#define LAUNCH(MPV, NLV) do { if (h.dc.nb == 5) LAUNCH1(MPV, NLV, 5); else LAUNCH1(MPV, NLV, 0); } while (0)
-  const int mp = h.dc.mp, nl = h.dc.nl;
-  if (const NlOps* ops = nl_ops(nl))
-    return ops->traj_env(h.dc, h.st, params, h.env_tab, pos, vel, h.plan_len, info_pos, info_vel, stream, g_err);
-  if (mp == MP_PROMP && nl == 2) LAUNCH(MP_PROMP, 2);
-  else if (mp == MP_PROMP && nl == 5) LAUNCH(MP_PROMP, 5);
-  else if (mp == MP_DMP && nl == 2) LAUNCH(MP_DMP, 2);
-  else if (mp == MP_DMP && nl == 5) LAUNCH(MP_DMP, 5);
-  else if (mp == MP_PRODMP && nl == 2) LAUNCH(MP_PRODMP, 2);
-  else if (mp == MP_PRODMP && nl == 5) LAUNCH(MP_PRODMP, 5);
-  else return fail(FGX_E_UNSUPPORTED, "n_links must be in 1..8");
-#undef LAUNCH1
-#undef LAUNCH
-  HIP_TRY(hipGetLastError());
-  return FGX_OK;
 }
 
 // ------------------------------------------------------------------------ config -> DevCfg
@@ -482,7 +414,7 @@ int fgx_create(const fgx_config* cfg, int64_t n_envs, int device, void** handle)
     delete[] sp;
     if (e != hipSuccess) { fgx_destroy(h); return fail(FGX_E_HIP, "hipMemcpy seeds"); }
   }
-  rc = launch_reset(*h, seeds, nullptr, -1, nullptr, 0);
+  rc = nl_ops(nl).reset(h->dc, h->st, seeds, nullptr, -1, nullptr, 0, g_err);
   if (rc) { fgx_destroy(h); return rc; }
   e = hipDeviceSynchronize();
   if (e != hipSuccess) { fgx_destroy(h); return fail(FGX_E_HIP, std::string("create sync: ") + hipGetErrorString(e)); }
@@ -539,7 +471,7 @@ int fgx_reset(void* handle, const uint64_t* seeds, const uint8_t* mask, int32_t 
   Handle* h = (Handle*)handle;
   if (!h) return fail(FGX_E_INVALID, "null handle");
   if (random_start < -1 || random_start > 1) return fail(FGX_E_INVALID, "random_start must be -1, 0 or 1");
-  return launch_reset(*h, seeds, mask, random_start, obs_out, (hipStream_t)stream);
+  return nl_ops(h->dc.nl).reset(h->dc, h->st, seeds, mask, random_start, obs_out, (hipStream_t)stream, g_err);
 }
 
 #ifdef FGX_STAMPS
@@ -633,20 +565,21 @@ int fgx_step(void* handle, const float* params, float* obs, double* ret, uint8_t
   }
   const int kernel = select_kernel(*h, h->learned() ? MP_GIVEN : h->dc.mp, o, h->learned());
   if (const int rc = attach_obs_scratch(h, o, kernel, (hipStream_t)stream)) return rc;
+  const NlOps& ops = nl_ops(h->dc.nl);
   if (h->learned()) {
     // per-env plans first (and, when requested, the time-major info copies), then the episode
     // over the given plans with per-env lengths
     float* P = h->plan_pos;
     float* V = h->plan_vel;
-    int rc = launch_traj_env(*h, params, P, V, (hipStream_t)stream, info ? info->positions : nullptr,
-                             info ? info->velocities : nullptr);
+    int rc = ops.traj_env(h->dc, h->st, params, h->env_tab, P, V, h->plan_len, info ? info->positions : nullptr,
+                          info ? info->velocities : nullptr, (hipStream_t)stream, g_err);
     if (rc) return rc;
-    Handle hh = *h;
-    hh.st.plan_len = h->plan_len;
+    DevState st = h->st;
+    st.plan_len = h->plan_len;
     // (params only for the validity checks of the raw tau / delay entries)
-    return launch_episode(hh, MP_GIVEN, kernel, params, P, V, o, (hipStream_t)stream);
+    return ops.episode(h->dc, st, MP_GIVEN, kernel, params, P, V, o, (hipStream_t)stream, g_err);
   }
-  return launch_episode(*h, h->dc.mp, kernel, params, nullptr, nullptr, o, (hipStream_t)stream);
+  return ops.episode(h->dc, h->st, h->dc.mp, kernel, params, nullptr, nullptr, o, (hipStream_t)stream, g_err);
 }
 
 int fgx_step_traj(void* handle, const float* des_pos, const float* des_vel, float* obs, double* ret,
@@ -667,16 +600,19 @@ int fgx_step_traj(void* handle, const float* des_pos, const float* des_vel, floa
   o.velocities = nullptr;   // the caller already holds the desired trajectories
   const int kernel = select_kernel(*h, MP_GIVEN, o, false);
   if (const int rc = attach_obs_scratch(h, o, kernel, (hipStream_t)stream)) return rc;
-  return launch_episode(*h, MP_GIVEN, kernel, nullptr, des_pos, des_vel, o, (hipStream_t)stream);
+  return nl_ops(h->dc.nl).episode(h->dc, h->st, MP_GIVEN, kernel, nullptr, des_pos, des_vel, o, (hipStream_t)stream,
+                                  g_err);
 }
 
 int fgx_trajectory(void* handle, const float* params, float* des_pos, float* des_vel, void* stream) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(FGX_E_INVALID, "null handle");
   if (!params || !des_pos || !des_vel) return fail(FGX_E_INVALID, "null argument");
-  if (h->learned()) return launch_traj_env(*h, params, des_pos, des_vel, (hipStream_t)stream);
-  if (const NlOps* ops = nl_ops(h->dc.nl)) return ops->traj(h->dc, h->st, params, des_pos, des_vel, (hipStream_t)stream, g_err);
-  return launch_trajectory(h->dc, h->st, params, des_pos, des_vel, (hipStream_t)stream, g_err);
+  const NlOps& ops = nl_ops(h->dc.nl);
+  if (h->learned())
+    return ops.traj_env(h->dc, h->st, params, h->env_tab, des_pos, des_vel, h->plan_len, nullptr, nullptr,
+                        (hipStream_t)stream, g_err);
+  return ops.traj(h->dc, h->st, params, des_pos, des_vel, (hipStream_t)stream, g_err);
 }
 
 int fgx_step_raw(void* handle, const float* actions, float* obs, double* reward, uint8_t* terminated,
@@ -685,31 +621,8 @@ int fgx_step_raw(void* handle, const float* actions, float* obs, double* reward,
   if (!h) return fail(FGX_E_INVALID, "null handle");
   if (!actions || !obs || !reward || !terminated || !truncated) return fail(FGX_E_INVALID, "null argument");
   if (h->dc.time_aware) return fail(FGX_E_UNSUPPORTED, "step-based envs have no TimeAwareObservation");
-  const int threads = kStepRawBlock;
-  const int blocks = (int)((h->dc.N + threads - 1) / threads);
-  hipStream_t s = (hipStream_t)stream;
-  // LDS rows of the workgroup's action / observation slices (k_step_raw)
-  const int so = step_raw_stride(h->dc.obs_dim), sa = step_raw_stride(h->dc.nl);
-  const size_t lds = sizeof(float) * threads * ((so > sa ? so : sa) + (final_obs ? so : 0));
-#define X(NL)                                                                                                  \
-  if (h->dc.nl == NL) {                                                                                        \
-    if (h->dc.env == ENV_SIMPLE)                                                                               \
-      hipLaunchKernelGGL((k_step_raw<ENV_SIMPLE, NL>), dim3(blocks), dim3(threads), lds, s, h->dc, h->st,        \
-                         actions, obs, reward, terminated, truncated, final_obs, autoreset);                   \
-    else if (h->dc.env == ENV_HOLE)                                                                            \
-      hipLaunchKernelGGL((k_step_raw<ENV_HOLE, NL>), dim3(blocks), dim3(threads), lds, s, h->dc, h->st,          \
-                         actions, obs, reward, terminated, truncated, final_obs, autoreset);                   \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_step_raw<ENV_VIA, NL>), dim3(blocks), dim3(threads), lds, s, h->dc, h->st,           \
-                         actions, obs, reward, terminated, truncated, final_obs, autoreset);                   \
-    HIP_TRY(hipGetLastError());                                                                                \
-    return FGX_OK;                                                                                             \
-  }
-  FGX_FOR_NL(X)
-#undef X
-  if (const NlOps* ops = nl_ops(h->dc.nl))
-    return ops->step_raw(h->dc, h->st, actions, obs, reward, terminated, truncated, final_obs, autoreset, lds, s, g_err);
-  return fail(FGX_E_UNSUPPORTED, "n_links must be in 1..8");
+  return nl_ops(h->dc.nl).step_raw(h->dc, h->st, actions, obs, reward, terminated, truncated, final_obs, autoreset,
+                                   (hipStream_t)stream, g_err);
 }
 
 int fgx_get_state(void* handle, double* q, double* qd, double* goal, double* hole, int32_t* steps, void* stream) {

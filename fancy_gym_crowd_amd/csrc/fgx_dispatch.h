@@ -1,53 +1,16 @@
 // fgx_dispatch.h — template dispatch of the episode kernel.  One translation unit per env kind
-// and basis specialisation (fgx_ep_<env>.hip: NB = 5, the registered configs; fgx_ep_<env>_gen.hip:
-// NB = 0, the generic runtime basis count), so that the build compiles them in parallel.  Which kernel
-// runs is decided before, once per step (fgx_select.h); this header only launches it.
+// and basis specialisation for 2 / 5 links (fgx_ep_<env>.hip: NB = 5, the registered configs;
+// fgx_ep_<env>_gen.hip: NB = 0, the generic runtime basis count) and one per further link count
+// (fgx_ep_nl.h, the logging kernel only), so that the build compiles them in parallel.  Which kernel
+// runs is decided before, once per step (fgx_select.h); this header only launches it.  What the units
+// export is declared in fgx_launch.h.
 #pragma once
 #include <string>
 
+#include "fgx_launch.h"
 #include "fgx_ws.h"
 #include "fgx_v2.h"
 #include "fgx_select.h"
-
-// returns 0 / FGX_E_* code, message in err; kernel: the EK_* id select_episode_kernel chose (fgx_select.h)
-#define FGX_DECLARE_LAUNCH(NAME)                                                                             \
-  int NAME(const fgx::DevCfg& c, const fgx::DevState& s, int mp, int kernel, const float* params,            \
-           const float* dpos, const float* dvel, const fgx::Outputs& o, hipStream_t stream, std::string& err);
-FGX_DECLARE_LAUNCH(fgx_launch_episode_simple)
-FGX_DECLARE_LAUNCH(fgx_launch_episode_hole)
-FGX_DECLARE_LAUNCH(fgx_launch_episode_via)
-FGX_DECLARE_LAUNCH(fgx_launch_episode_simple_gen)
-FGX_DECLARE_LAUNCH(fgx_launch_episode_hole_gen)
-FGX_DECLARE_LAUNCH(fgx_launch_episode_via_gen)
-#undef FGX_DECLARE_LAUNCH
-// k_episode_jl instantiations (fgx_ep_jl.hip): nbs = the compiled basis count (5, or 0 = generic)
-int fgx_launch_episode_jl(const fgx::DevCfg& c, const fgx::DevState& s, int mp, int nbs, const float* params,
-                          const fgx::Outputs& o, hipStream_t stream, std::string& err);
-
-namespace fgx {
-// Link counts other than the registered 2 and 5 (include/fgx.h: n_links 1..8; base_reacher.py:17-39
-// takes any count and bb_env_constructor forwards env kwargs, envs/registry.py:280-281): one
-// translation unit per count (fgx_ep_nl<n>.hip -> fgx_ep_nl.h) with the logging k_episode for every
-// env kind / MP kind / controller plus the reset, step-based, trajectory and learned-phase kernels.
-struct NlOps {
-  int (*episode)(const DevCfg& c, const DevState& s, int mp, int kernel, const float* params, const float* dpos,
-                 const float* dvel, const Outputs& o, hipStream_t stream, std::string& err);
-  int (*reset)(const DevCfg& c, const DevState& s, const uint64_t* seeds, const uint8_t* mask, int rs_mode, float* obs,
-               hipStream_t stream, std::string& err);
-  int (*step_raw)(const DevCfg& c, const DevState& s, const float* act, float* obs, double* rew, uint8_t* term,
-                  uint8_t* trunc, float* final_obs, int autoreset, size_t lds, hipStream_t stream, std::string& err);
-  int (*traj)(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel, hipStream_t stream,
-              std::string& err);
-  int (*traj_env)(const DevCfg& c, const DevState& s, const float* params, float* env_tab, float* dpos, float* dvel,
-                  int32_t* plan_len, float* info_pos, float* info_vel, hipStream_t stream, std::string& err);
-};
-}  // namespace fgx
-const fgx::NlOps* fgx_nl_ops_1();
-const fgx::NlOps* fgx_nl_ops_3();
-const fgx::NlOps* fgx_nl_ops_4();
-const fgx::NlOps* fgx_nl_ops_6();
-const fgx::NlOps* fgx_nl_ops_7();
-const fgx::NlOps* fgx_nl_ops_8();
 
 namespace fgx {
 

@@ -3,6 +3,7 @@
 #include <cstdlib>
 
 #include "fgx_hp.h"
+#include "fgx_launch.h"
 
 namespace fgx {
 

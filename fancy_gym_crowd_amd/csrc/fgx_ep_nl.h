@@ -1,11 +1,16 @@
-// fgx_ep_nl.h — every kernel family of one link count FGX_NL outside the registered 2 and 5
-// (include/fgx.h n_links 1..8; the reference env takes any n_links, base_reacher.py:17-39, and
+// fgx_ep_nl.h — what a handle of FGX_NL links launches: the NlOps table (fgx_launch.h) of one link
+// count (include/fgx.h n_links 1..8; the reference env takes any n_links, base_reacher.py:17-39, and
 // bb_env_constructor forwards env kwargs, envs/registry.py:280-281).  Included once by each
-// fgx_ep_nl<n>.hip, which defines FGX_NL, so that the counts compile in parallel.  The episode is the
-// logging k_episode (fgx_dispatch.h LOG_ONLY: it serves every info level and the validity checks) on
-// the generic basis count (NB = 0, any n_basis <= 12); reset, step-based step, trajectories and the
-// learned-phase plans are the same templates the registered counts use.  Sums over the joints follow
-// numpy's order at every count (np_sum, fgx_device.h: the pairwise tree at 8).
+// fgx_ep_nl<n>.hip, which defines FGX_NL, so that the counts compile in parallel.  Reset, step-based
+// step, trajectories and the learned-phase plans are the same templates at every count.  The
+// registered counts 2 and 5 differ in three places, all below (kRegistered<NL>):
+//   * NB: they also hold the NB = 5 forms of k_traj_valu / k_traj_env (kNB5<NL>; the others: the
+//     generic basis count NB = 0 only, any n_basis <= 12);
+//   * traj: they try k_traj_mfma first;
+//   * episode: their episode kernels live in the env-kind units (fgx_ep_<env>[_gen].hip, fgx_ep_jl.hip,
+//     fgx_ep_hp.hip) and this unit only routes to them; the others hold the logging k_episode here
+//     (fgx_dispatch.h LOG_ONLY: it serves every info level and the validity checks).
+// Sums over the joints follow numpy's order at every count (np_sum, fgx_device.h: the pairwise tree at 8).
 #pragma once
 #include "fgx_dispatch.h"
 #include "fgx_learned.h"
@@ -17,73 +22,107 @@
 
 namespace {
 using namespace fgx;
-constexpr int NLV = FGX_NL;
+template <int NL>
+constexpr bool kRegistered = NL == 2 || NL == 5;
+// the compiled basis count besides the generic NB = 0 (the registered counts: 5; the others: none)
+template <int NL>
+constexpr int kNB5 = kRegistered<NL> ? 5 : 0;
 
+// (templates on the count, so that `if constexpr` leaves the branch not taken uninstantiated)
+template <int NL>
 int nl_episode(const DevCfg& c, const DevState& s, int mp, int kernel, const float* params, const float* dpos,
                const float* dvel, const Outputs& o, hipStream_t stream, std::string& err) {
-  switch (c.env) {
-    case ENV_SIMPLE: return launch_episode_env<ENV_SIMPLE, 0, NLV>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
-    case ENV_HOLE: return launch_episode_env<ENV_HOLE, 0, NLV>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
-    case ENV_VIA: return launch_episode_env<ENV_VIA, 0, NLV>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
+  if constexpr (kRegistered<NL>) {
+    // HoleReacher up to info level 1: the producer / consumer pipeline (fgx_hp.h)
+    if (kernel == EK_HP) return fgx_launch_episode_hp(c, s, mp, params, o, stream, err);
+    const bool gen = mp != MP_GIVEN && c.nb != 5;   // generic basis-count instantiations
+    switch (c.env) {
+      case ENV_SIMPLE:
+        return (gen ? fgx_launch_episode_simple_gen : fgx_launch_episode_simple)(c, s, mp, kernel, params, dpos, dvel, o,
+                                                                               stream, err);
+      case ENV_HOLE:
+        return (gen ? fgx_launch_episode_hole_gen : fgx_launch_episode_hole)(c, s, mp, kernel, params, dpos, dvel, o,
+                                                                           stream, err);
+      case ENV_VIA:
+        return (gen ? fgx_launch_episode_via_gen : fgx_launch_episode_via)(c, s, mp, kernel, params, dpos, dvel, o,
+                                                                         stream, err);
+    }
+  } else {
+    switch (c.env) {
+      case ENV_SIMPLE: return launch_episode_env<ENV_SIMPLE, 0, NL>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
+      case ENV_HOLE: return launch_episode_env<ENV_HOLE, 0, NL>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
+      case ENV_VIA: return launch_episode_env<ENV_VIA, 0, NL>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
+    }
   }
   err = "bad env kind";
   return -1;
 }
 
+template <int NL>
 int nl_reset(const DevCfg& c, const DevState& s, const uint64_t* seeds, const uint8_t* mask, int rs_mode, float* obs,
              hipStream_t stream, std::string& err) {
   const int threads = 256;
-  hipLaunchKernelGGL((k_reset<NLV>), dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s,
+  hipLaunchKernelGGL((k_reset<NL>), dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s,
                      seeds, mask, rs_mode, obs);
   return launch_status("k_reset", err);
 }
 
+template <int NL>
 int nl_step_raw(const DevCfg& c, const DevState& s, const float* act, float* obs, double* rew, uint8_t* term,
-                uint8_t* trunc, float* final_obs, int autoreset, size_t lds, hipStream_t stream, std::string& err) {
+                uint8_t* trunc, float* final_obs, int autoreset, hipStream_t stream, std::string& err) {
   const dim3 grid((unsigned)((c.N + kStepRawBlock - 1) / kStepRawBlock)), block(kStepRawBlock);
-  if (c.env == ENV_SIMPLE)
-    hipLaunchKernelGGL((k_step_raw<ENV_SIMPLE, NLV>), grid, block, lds, stream, c, s, act, obs, rew, term, trunc,
-                       final_obs, autoreset);
-  else if (c.env == ENV_HOLE)
-    hipLaunchKernelGGL((k_step_raw<ENV_HOLE, NLV>), grid, block, lds, stream, c, s, act, obs, rew, term, trunc,
-                       final_obs, autoreset);
-  else
-    hipLaunchKernelGGL((k_step_raw<ENV_VIA, NLV>), grid, block, lds, stream, c, s, act, obs, rew, term, trunc,
-                       final_obs, autoreset);
+  // LDS rows of the workgroup's action / observation slices (k_step_raw)
+  const int so = step_raw_stride(c.obs_dim), sa = step_raw_stride(NL);
+  const size_t lds = sizeof(float) * kStepRawBlock * ((so > sa ? so : sa) + (final_obs ? so : 0));
+  const auto k = c.env == ENV_SIMPLE ? k_step_raw<ENV_SIMPLE, NL>
+                 : c.env == ENV_HOLE ? k_step_raw<ENV_HOLE, NL>
+                                     : k_step_raw<ENV_VIA, NL>;
+  hipLaunchKernelGGL(k, grid, block, lds, stream, c, s, act, obs, rew, term, trunc, final_obs, autoreset);
   return launch_status("k_step_raw", err);
 }
 
+// K<MP, NL, NB> of the handle's MP kind and basis count (one function type per K); null: no MP
+#define FGX_NL_KERNEL_MP(K, NB) \
+  (c.mp == MP_PROMP ? K<MP_PROMP, NL, NB> : c.mp == MP_DMP ? K<MP_DMP, NL, NB> : c.mp == MP_PRODMP ? K<MP_PRODMP, NL, NB> : nullptr)
+#define FGX_NL_KERNEL(K) (c.nb == kNB5<NL> ? FGX_NL_KERNEL_MP(K, kNB5<NL>) : FGX_NL_KERNEL_MP(K, 0))
+
+// k_traj_mfma (2 / 5 links), else k_traj_run, else k_traj_valu: the first that takes the plan
+template <int NL>
 int nl_traj(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel, hipStream_t stream,
             std::string& err) {
-  const int rr = launch_traj_run<NLV>(c, s, params, dpos, dvel, stream);
-  if (rr == 0) return 0;
-  if (rr == 2) return launch_status("k_traj_run", err);
+  const auto valu = FGX_NL_KERNEL(k_traj_valu);
+  if (!valu) {
+    err = "step-based handle has no trajectory generator";
+    return -1;
+  }
+  if constexpr (kRegistered<NL>)
+    if (const int rm = launch_traj_mfma<NL>(c, s, params, dpos, dvel, stream, err); rm != 1) return rm;
+  if (const int rr = launch_traj_run<NL>(c, s, params, dpos, dvel, stream, err); rr != 1) return rr;
   const int threads = 256;
-  const dim3 grid((unsigned)((c.N + threads - 1) / threads)), block(threads);
-  if (c.mp == MP_PROMP) hipLaunchKernelGGL((k_traj_valu<MP_PROMP, NLV, 0>), grid, block, 0, stream, c, s, params, dpos, dvel);
-  else if (c.mp == MP_DMP) hipLaunchKernelGGL((k_traj_valu<MP_DMP, NLV, 0>), grid, block, 0, stream, c, s, params, dpos, dvel);
-  else if (c.mp == MP_PRODMP) hipLaunchKernelGGL((k_traj_valu<MP_PRODMP, NLV, 0>), grid, block, 0, stream, c, s, params, dpos, dvel);
-  else { err = "step-based handle has no trajectory generator"; return -1; }
+  hipLaunchKernelGGL(valu, dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s, params, dpos,
+                     dvel);
   return launch_status("k_traj_valu", err);
 }
 
+template <int NL>
 int nl_traj_env(const DevCfg& c, const DevState& s, const float* params, float* env_tab, float* dpos, float* dvel,
                 int32_t* plan_len, float* info_pos, float* info_vel, hipStream_t stream, std::string& err) {
+  const auto k = FGX_NL_KERNEL(k_traj_env);
+  if (!k) {
+    err = "learned phase parameters need a movement primitive";
+    return -1;
+  }
   const int threads = 256;
-  const dim3 grid((unsigned)((c.N + threads - 1) / threads)), block(threads);
-#define FGX_NL_TRAJ_ENV(MPV)                                                                                  \
-  hipLaunchKernelGGL((k_traj_env<MPV, NLV, 0>), grid, block, 0, stream, c, s, params, env_tab, dpos, dvel, plan_len, \
-                     info_pos, info_vel)
-  if (c.mp == MP_PROMP) FGX_NL_TRAJ_ENV(MP_PROMP);
-  else if (c.mp == MP_DMP) FGX_NL_TRAJ_ENV(MP_DMP);
-  else if (c.mp == MP_PRODMP) FGX_NL_TRAJ_ENV(MP_PRODMP);
-  else { err = "learned phase parameters need a movement primitive"; return -1; }
-#undef FGX_NL_TRAJ_ENV
+  hipLaunchKernelGGL(k, dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s, params, env_tab,
+                     dpos, dvel, plan_len, info_pos, info_vel);
   return launch_status("k_traj_env", err);
 }
+#undef FGX_NL_KERNEL
+#undef FGX_NL_KERNEL_MP
 }  // namespace
 
 const fgx::NlOps* FGX_NL_CAT(fgx_nl_ops_, FGX_NL)() {
-  static const fgx::NlOps ops = {nl_episode, nl_reset, nl_step_raw, nl_traj, nl_traj_env};
+  static const fgx::NlOps ops = {nl_episode<FGX_NL>, nl_reset<FGX_NL>, nl_step_raw<FGX_NL>, nl_traj<FGX_NL>,
+                                 nl_traj_env<FGX_NL>};
   return &ops;
 }

@@ -620,7 +620,3 @@ inline size_t hp_lds_bytes(int nl, int groups) {
 static_assert(4 * HpLayout<5>::GROUP * sizeof(double) <= 160 * 1024, "k_episode_hp: four groups fit one CU's LDS");
 
 }  // namespace fgx
-
-// fgx_ep_hp.hip
-int fgx_launch_episode_hp(const fgx::DevCfg& c, const fgx::DevState& s, int mp, const float* params,
-                          const fgx::Outputs& o, hipStream_t stream, std::string& err);

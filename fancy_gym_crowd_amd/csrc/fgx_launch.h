@@ -1,0 +1,52 @@
+// fgx_launch.h — the launch functions the translation units offer each other: declarations only, so
+// the C ABI unit (fgx_api.hip) reaches every kernel family without seeing a kernel template.
+// All return 0 or an FGX_E_* code (-1 bad kind / no MP, -2 HIP error, -4 not instantiated), message in err.
+#pragma once
+#include <string>
+
+#include "fgx_device.h"
+
+// k_episode and its variants per env kind (fgx_ep_<env>.hip: NB = 5; fgx_ep_<env>_gen.hip: NB = 0), 2 / 5
+// links; kernel: the EK_* id select_episode_kernel chose (fgx_select.h)
+#define FGX_DECLARE_LAUNCH(NAME)                                                                             \
+  int NAME(const fgx::DevCfg& c, const fgx::DevState& s, int mp, int kernel, const float* params,            \
+           const float* dpos, const float* dvel, const fgx::Outputs& o, hipStream_t stream, std::string& err);
+FGX_DECLARE_LAUNCH(fgx_launch_episode_simple)
+FGX_DECLARE_LAUNCH(fgx_launch_episode_hole)
+FGX_DECLARE_LAUNCH(fgx_launch_episode_via)
+FGX_DECLARE_LAUNCH(fgx_launch_episode_simple_gen)
+FGX_DECLARE_LAUNCH(fgx_launch_episode_hole_gen)
+FGX_DECLARE_LAUNCH(fgx_launch_episode_via_gen)
+#undef FGX_DECLARE_LAUNCH
+// k_episode_jl instantiations (fgx_ep_jl.hip): nbs = the compiled basis count (5, or 0 = generic)
+int fgx_launch_episode_jl(const fgx::DevCfg& c, const fgx::DevState& s, int mp, int nbs, const float* params,
+                          const fgx::Outputs& o, hipStream_t stream, std::string& err);
+// k_episode_hp instantiations (fgx_ep_hp.hip)
+int fgx_launch_episode_hp(const fgx::DevCfg& c, const fgx::DevState& s, int mp, const float* params,
+                          const fgx::Outputs& o, hipStream_t stream, std::string& err);
+
+namespace fgx {
+// What a handle launches, per link count (include/fgx.h: n_links 1..8; base_reacher.py:17-39 takes any
+// count and bb_env_constructor forwards env kwargs, envs/registry.py:280-281): one translation unit
+// per count (fgx_ep_nl<n>.hip -> fgx_ep_nl.h) fills this table, and fgx_api.hip launches through it only.
+struct NlOps {
+  int (*episode)(const DevCfg& c, const DevState& s, int mp, int kernel, const float* params, const float* dpos,
+                 const float* dvel, const Outputs& o, hipStream_t stream, std::string& err);
+  int (*reset)(const DevCfg& c, const DevState& s, const uint64_t* seeds, const uint8_t* mask, int rs_mode, float* obs,
+               hipStream_t stream, std::string& err);
+  int (*step_raw)(const DevCfg& c, const DevState& s, const float* act, float* obs, double* rew, uint8_t* term,
+                  uint8_t* trunc, float* final_obs, int autoreset, hipStream_t stream, std::string& err);
+  int (*traj)(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel, hipStream_t stream,
+              std::string& err);
+  int (*traj_env)(const DevCfg& c, const DevState& s, const float* params, float* env_tab, float* dpos, float* dvel,
+                  int32_t* plan_len, float* info_pos, float* info_vel, hipStream_t stream, std::string& err);
+};
+}  // namespace fgx
+const fgx::NlOps* fgx_nl_ops_1();
+const fgx::NlOps* fgx_nl_ops_2();
+const fgx::NlOps* fgx_nl_ops_3();
+const fgx::NlOps* fgx_nl_ops_4();
+const fgx::NlOps* fgx_nl_ops_5();
+const fgx::NlOps* fgx_nl_ops_6();
+const fgx::NlOps* fgx_nl_ops_7();
+const fgx::NlOps* fgx_nl_ops_8();

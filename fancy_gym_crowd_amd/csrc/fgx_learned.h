@@ -1,5 +1,5 @@
 // fgx_learned.h — per-env movement primitives for learned tau / delay and sub-trajectories
-// (included by fgx_api.hip only).
+// (instantiated by the per-link-count units, fgx_ep_nl.h).
 //
 // Reference: make_env_helpers.py:115-126 (learn_tau / learn_delay, tau_bound [2 dt, duration],
 // delay_bound [0, duration - 2 dt]), black_box_wrapper.py:106-140 (get_trajectory: np.clip of the

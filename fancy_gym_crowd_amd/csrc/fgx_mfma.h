@@ -470,24 +470,21 @@ inline void launch_lds(const void* kernel, size_t lds, F&& launch) {
   launch();
 }
 
+// 0: launched; 1: not applicable (the caller goes on to k_traj_run); -2: launch error, message in err
+template <int NL>
 inline int launch_traj_mfma(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel,
-                            hipStream_t stream) {
+                            hipStream_t stream, std::string& err) {
+  if (c.nl != NL || (c.mp != MP_PROMP && c.mp != MP_PRODMP)) return 1;
   if (c.replan != 0 || c.nb != 5 || c.cond_desired || (c.T % 4) != 0) return 1;   // per-env plan starts: VALU kernel
   if (((uintptr_t)dpos | (uintptr_t)dvel) & 15) return 1;
   if ((int64_t)c.T * c.nl * 4 * 32 >= (int64_t)1 << 31) return 1;   // (32-bit run offsets)
   const bool r3 = std::getenv("FGX_TRAJ_R3") != nullptr;   // A/B: the round-3 kernel
   if (r3) {
     const int64_t groups = (c.N + 31) / 32;
-    const int blocks = (int)((groups + kTrajWaves - 1) / kTrajWaves);
-#define X(NL)                                                                                                  \
-    if (c.nl == NL) {                                                                                          \
-      if (c.mp == MP_PROMP) hipLaunchKernelGGL((k_traj_mfma_r3<MP_PROMP, NL>), dim3(blocks), dim3(64 * kTrajWaves), 0, stream, c, s, params, dpos, dvel); \
-      else hipLaunchKernelGGL((k_traj_mfma_r3<MP_PRODMP, NL>), dim3(blocks), dim3(64 * kTrajWaves), 0, stream, c, s, params, dpos, dvel); \
-      return hipGetLastError() == hipSuccess ? 0 : 2;                                                          \
-    }
-    X(2) X(5)
-#undef X
-    return 1;
+    const dim3 grid((unsigned)((groups + kTrajWaves - 1) / kTrajWaves)), block(64 * kTrajWaves);
+    if (c.mp == MP_PROMP) hipLaunchKernelGGL((k_traj_mfma_r3<MP_PROMP, NL>), grid, block, 0, stream, c, s, params, dpos, dvel);
+    else hipLaunchKernelGGL((k_traj_mfma_r3<MP_PRODMP, NL>), grid, block, 0, stream, c, s, params, dpos, dvel);
+    return launch_status("k_traj_mfma_r3", err);
   }
   const size_t lds = traj_mfma_lds_bytes(c.rows, c.stride, c.T, c.mp, c.nl);
   if (lds > 160 * 1024) return 1;   // (a table this long: the VALU kernel)
@@ -495,17 +492,12 @@ inline int launch_traj_mfma(const DevCfg& c, const DevState& s, const float* par
   const int64_t groups = (c.N + kTrajGE - 1) / kTrajGE;
   int blocks = (int)std::min<int64_t>(groups, 256);
   if (const char* gv = std::getenv("FGX_TRAJ_GRID")) blocks = (int)std::max<int64_t>(1, std::min<int64_t>(groups, std::atoll(gv)));
-#define X(NL)                                                                                                  \
-  if (c.nl == NL) {                                                                                            \
-    if (c.mp == MP_PROMP)                                                                                      \
-      launch_lds((const void*)k_traj_mfma<MP_PROMP, NL>, lds, [&] { hipLaunchKernelGGL((k_traj_mfma<MP_PROMP, NL>), dim3(blocks), dim3(64 * kTrajGWaves), lds, stream, c, s, params, dpos, dvel); }); \
-    else                                                                                                       \
-      launch_lds((const void*)k_traj_mfma<MP_PRODMP, NL>, lds, [&] { hipLaunchKernelGGL((k_traj_mfma<MP_PRODMP, NL>), dim3(blocks), dim3(64 * kTrajGWaves), lds, stream, c, s, params, dpos, dvel); }); \
-    return hipGetLastError() == hipSuccess ? 0 : 2;                                                            \
-  }
-  X(2) X(5)
-#undef X
-  return 1;
+  const dim3 grid(blocks), block(64 * kTrajGWaves);
+  if (c.mp == MP_PROMP)
+    launch_lds((const void*)k_traj_mfma<MP_PROMP, NL>, lds, [&] { hipLaunchKernelGGL((k_traj_mfma<MP_PROMP, NL>), grid, block, lds, stream, c, s, params, dpos, dvel); });
+  else
+    launch_lds((const void*)k_traj_mfma<MP_PRODMP, NL>, lds, [&] { hipLaunchKernelGGL((k_traj_mfma<MP_PRODMP, NL>), grid, block, lds, stream, c, s, params, dpos, dvel); });
+  return launch_status("k_traj_mfma", err);
 }
 
 }  // namespace fgx

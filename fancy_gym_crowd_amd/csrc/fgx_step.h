@@ -1,7 +1,7 @@
 // fgx_step.h — k_step_raw: one step-based env.step for all envs (the per-substep kernel of the
 // step-based ids 'fancy/{Simple,LongSimple,Hole,ViaPoint}Reacher-v0'; base_reacher.py:98-119,
-// base_reacher_torque.py:20-37, base_reacher_direct.py).  Own header: only fgx_api.hip
-// instantiates it, so the episode units do not recompile for it.
+// base_reacher_torque.py:20-37, base_reacher_direct.py).  Own header: only the
+// per-link-count units (fgx_ep_nl.h) instantiate it, so the episode units do not recompile for it.
 #pragma once
 #include "fgx_kernels.h"
 
@@ -13,7 +13,7 @@ namespace fgx {
 // wave-instruction of the HBM side reads / writes 64 consecutive floats (256 B) instead of one
 // float per lane at a NL·4 / obs_dim·4-byte stride.  LDS rows use an odd stride (no bank
 // conflicts for the per-thread row accesses).  Dynamic LDS: kStepRawBlock · (NL + 1 | od + 1)
-// floats, twice with final_obs (fgx_step_raw sizes it).
+// floats, twice with final_obs (nl_step_raw, fgx_ep_nl.h, sizes it).
 constexpr int kStepRawBlock = 256;
 __host__ __device__ constexpr int step_raw_stride(int w) { return w | 1; }
 

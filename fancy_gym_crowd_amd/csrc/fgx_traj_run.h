@@ -32,17 +32,6 @@ namespace fgx {
 
 constexpr int kTrajRunThreads = 256;
 
-inline int traj_run_cus() {
-  static const int n = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
-
 // V4: every piece is a whole number of 16-B chunks at a 16-B aligned address (host-checked)
 template <int MP, int NL, int NB, bool V4>
 __global__ __launch_bounds__(kTrajRunThreads) void k_traj_run(DevCfg c, DevState s, const float* __restrict__ params,
@@ -312,10 +301,10 @@ inline TrajRunShape traj_run_shape(const DevCfg& c) {
   return {GE, RC, nt, sep, threads, per_cu, lds};
 }
 
-// 0: launched; 1: not applicable (the caller runs k_traj_valu); 2: launch error
+// 0: launched; 1: not applicable (the caller runs k_traj_valu); -2: launch error, message in err
 template <int NL>
 inline int launch_traj_run(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel,
-                           hipStream_t stream) {
+                           hipStream_t stream, std::string& err) {
   if (std::getenv("FGX_TRAJ_VALU")) return 1;   // A/B: the one-env-per-lane kernel
   if (c.nl != NL || c.T <= 0) return 1;
   const TrajRunShape sh = traj_run_shape(c);
@@ -323,7 +312,7 @@ inline int launch_traj_run(const DevCfg& c, const DevState& s, const float* para
   const bool v4 = ((c.T * NL) % 4) == 0 && ((sh.RC * NL) % 4) == 0 && (((uintptr_t)dpos | (uintptr_t)dvel) & 15) == 0;
   const int64_t groups = (c.N + sh.GE - 1) / sh.GE;
   const int nt = sh.nt;
-  const int blocks = (int)std::min<int64_t>(groups, (int64_t)traj_run_cus() * sh.per_cu);
+  const int blocks = (int)std::min<int64_t>(groups, (int64_t)device_cus() * sh.per_cu);
   const dim3 grid(blocks), block(sh.threads);
 #define RUN(MPV, NBV, V4V)                                                                                      \
   launch_lds((const void*)k_traj_run<MPV, NL, NBV, V4V>, sh.lds, [&] {                                        \
@@ -341,7 +330,7 @@ inline int launch_traj_run(const DevCfg& c, const DevState& s, const float* para
 #undef BY_NB
 #undef BY_V4
 #undef RUN
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return launch_status("k_traj_run", err);
 }
 
 }  // namespace fgx
