@@ -297,10 +297,8 @@ const char* fgx_last_error(void) { return g_err.c_str(); }
 int fgx_selftest_sincos(const double* x, int64_t n, double* out, void* stream) {
   if (!x || !out || n < 0) return fail(FGX_E_INVALID, "bad argument");
   if (n == 0) return FGX_OK;
-  hipLaunchKernelGGL(k_selftest_sincos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n,
-                     out);
-  HIP_TRY(hipGetLastError());
-  return FGX_OK;
+  return launch("k_selftest_sincos", k_selftest_sincos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                (hipStream_t)stream, g_err, x, n, out);
 }
 
 int fgx_abi_version(void) { return FGX_ABI_VERSION; }

@@ -40,8 +40,8 @@ inline int fgx_transpose_state(const fgx::DevCfg& c, const fgx::DevState& s, dou
                                double* hole, int32_t* steps, hipStream_t stream, std::string& err) {
   const int threads = 256;
   const int blocks = (int)((c.N + threads - 1) / threads);
-  hipLaunchKernelGGL(fgx::k_get_state, dim3(blocks), dim3(threads), 0, stream, c, s, q, qd, goal, hole, steps);
-  return fgx::launch_status("k_get_state", err);
+  return fgx::launch("k_get_state", fgx::k_get_state, dim3(blocks), dim3(threads), 0, stream, err, c, s, q, qd, goal, hole,
+                     steps);
 }
 
 inline int fgx_untranspose_state(const fgx::DevCfg& c, const fgx::DevState& s, const double* q, const double* qd,
@@ -49,6 +49,6 @@ inline int fgx_untranspose_state(const fgx::DevCfg& c, const fgx::DevState& s, c
                                  std::string& err) {
   const int threads = 256;
   const int blocks = (int)((c.N + threads - 1) / threads);
-  hipLaunchKernelGGL(fgx::k_set_state, dim3(blocks), dim3(threads), 0, stream, c, s, q, qd, goal, hole, steps);
-  return fgx::launch_status("k_set_state", err);
+  return fgx::launch("k_set_state", fgx::k_set_state, dim3(blocks), dim3(threads), 0, stream, err, c, s, q, qd, goal, hole,
+                     steps);
 }

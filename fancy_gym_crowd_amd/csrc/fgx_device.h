@@ -62,6 +62,19 @@ inline int launch_status(const char* what, std::string& err) {
   return -2;
 }
 
+// Host: the one way a kernel is launched: the dynamic-LDS limit raised where `lds` needs it, the
+// launch, its status under the name `what`.  0, or -2 with the message in err.
+template <class... P, class... A>
+inline int launch(const char* what, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                  std::string& err, const A&... args) {
+  if (raise_lds_limit((const void*)kernel, lds) != hipSuccess) {
+    err = std::string(what) + ": cannot raise the dynamic LDS limit";
+    return -2;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+  return launch_status(what, err);
+}
+
 constexpr int kMaxLinks = 8;
 constexpr int kMaxObs = 3 * kMaxLinks + 5;
 constexpr int kMaxBasis = 16;

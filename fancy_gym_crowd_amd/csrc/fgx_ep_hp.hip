@@ -23,50 +23,12 @@ static int launch_hp(const DevCfg& c, const DevState& s, const float* params, co
     return -1;
   }
   const size_t lds = hp_lds_bytes(5, G);
-  if (raise_lds_limit((const void*)k_episode_hp<MP, CTRL, 5, 5, G, INFO>, lds) != hipSuccess) {
-    err = "k_episode_hp: cannot raise the dynamic LDS limit";
-    return -2;
-  }
   const int64_t per = 64 * G;
-  hipLaunchKernelGGL((k_episode_hp<MP, CTRL, 5, 5, G, INFO>), dim3((unsigned)((c.N + per - 1) / per)), dim3(192 * G), lds,
-                     stream, c, s, params, o);
-  if (const int rc = launch_status("k_episode_hp launch", err)) return rc;
-  hipLaunchKernelGGL((k_hp_finish<5, CTRL != CTRL_PD>), dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, stream, c, s,
-                     o);
-  return launch_status("k_hp_finish launch", err);
-}
-
-template <int MP, int G>
-static int launch_hp_ctrl(const DevCfg& c, const DevState& s, const float* params, const Outputs& o, hipStream_t stream,
-                          std::string& err) {
-  const bool info = hp_info_rows(o);
-#ifdef FGX_HP_ONLY_CFG3   // diagnostics builds (tools/unit_variant.py): config 3's instantiation only
-  if (MP == MP_PRODMP && c.ctrl == CTRL_PD && !info) return launch_hp<MP_PRODMP, CTRL_PD, G, false>(c, s, params, o, stream, err);
-  err = "FGX_HP_ONLY_CFG3 build";
-  return -1;
-#endif
-  switch (c.ctrl) {
-    case CTRL_PD: return info ? launch_hp<MP, CTRL_PD, G, true>(c, s, params, o, stream, err)
-                              : launch_hp<MP, CTRL_PD, G, false>(c, s, params, o, stream, err);
-    case CTRL_VEL: return info ? launch_hp<MP, CTRL_VEL, G, true>(c, s, params, o, stream, err)
-                               : launch_hp<MP, CTRL_VEL, G, false>(c, s, params, o, stream, err);
-    case CTRL_POS: return info ? launch_hp<MP, CTRL_POS, G, true>(c, s, params, o, stream, err)
-                               : launch_hp<MP, CTRL_POS, G, false>(c, s, params, o, stream, err);
-  }
-  err = "bad ctrl_kind";
-  return -1;
-}
-
-template <int G>
-static int launch_hp_mp(const DevCfg& c, const DevState& s, int mp, const float* params, const Outputs& o,
-                        hipStream_t stream, std::string& err) {
-  switch (mp) {
-    case MP_PROMP: return launch_hp_ctrl<MP_PROMP, G>(c, s, params, o, stream, err);
-    case MP_DMP: return launch_hp_ctrl<MP_DMP, G>(c, s, params, o, stream, err);
-    case MP_PRODMP: return launch_hp_ctrl<MP_PRODMP, G>(c, s, params, o, stream, err);
-  }
-  err = "k_episode_hp: bad mp kind";
-  return -1;
+  if (const int rc = launch("k_episode_hp launch", k_episode_hp<MP, CTRL, 5, 5, G, INFO>,
+                            dim3((unsigned)((c.N + per - 1) / per)), dim3(192 * G), lds, stream, err, c, s, params, o))
+    return rc;
+  return launch("k_hp_finish launch", k_hp_finish<5, CTRL != CTRL_PD>, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0,
+                stream, err, c, s, o);
 }
 
 }  // namespace fgx
@@ -75,12 +37,26 @@ static int launch_hp_mp(const DevCfg& c, const DevState& s, int mp, const float*
 // way; one group per workgroup below (FGX_HP_G=1 / 4 forces)
 int fgx_launch_episode_hp(const fgx::DevCfg& c, const fgx::DevState& s, int mp, const float* params,
                           const fgx::Outputs& o, hipStream_t stream, std::string& err) {
+  using namespace fgx;
   if (c.nl != 5 || c.nb != 5) {
     err = "k_episode_hp: 5 links and 5 basis functions only";
     return -4;
   }
-  int G = (c.N >= (int64_t)fgx::device_cus() * 256) ? 4 : 1;   // (a full round: 256 envs per CU)
+  int G = (c.N >= (int64_t)device_cus() * 256) ? 4 : 1;   // (a full round: 256 envs per CU)
   if (const char* v = std::getenv("FGX_HP_G")) G = std::atoi(v) == 4 ? 4 : 1;
-  return G == 4 ? fgx::launch_hp_mp<4>(c, s, mp, params, o, stream, err)
-                : fgx::launch_hp_mp<1>(c, s, mp, params, o, stream, err);
+  return pick<4, 1>(G, -4, "k_episode_hp: group count not instantiated", err, [&](auto GV) {
+    return pick<MP_PROMP, MP_DMP, MP_PRODMP>(mp, -1, "k_episode_hp: bad mp kind", err, [&](auto MP) {
+      return pick<CTRL_PD, CTRL_VEL, CTRL_POS>(c.ctrl, -1, "bad ctrl_kind", err, [&](auto CTRL) {
+        return pick<0, 1>(hp_info_rows(o), -1, "", err, [&](auto INFO) {
+#ifdef FGX_HP_ONLY_CFG3   // diagnostics builds (tools/unit_variant.py): config 3's instantiation only
+          if constexpr (MP != MP_PRODMP || CTRL != CTRL_PD || INFO != 0 || GV != 4) {
+            err = "FGX_HP_ONLY_CFG3 build";
+            return -1;
+          } else
+#endif
+          return launch_hp<MP, CTRL, GV, INFO != 0>(c, s, params, o, stream, err);
+        });
+      });
+    });
+  });
 }

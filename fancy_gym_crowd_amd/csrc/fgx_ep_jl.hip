@@ -27,44 +27,26 @@ int launch_jl(const fgx::DevCfg& c, const fgx::DevState& s, const float* params,
   // slot per CU (32768 envs 45.2 -> 48.2 us, profiles/r06_jl_resetwave_ab.log).  FGX_JL_RW=0 / 1: A/B
   int rw = blocks <= (unsigned)fgx::device_cus() ? 1 : 0;
   if (const char* v = std::getenv("FGX_JL_RW")) rw = v[0] == '1' ? 1 : 0;
-  hipLaunchKernelGGL((fgx::k_episode_jl<MP, NL, NB>), dim3(blocks), dim3(S::THREADS + 64 * rw), S::lds_bytes(),
-                     stream, c, s, params, o, gw, rw);
-  return fgx::launch_status("k_episode_jl launch", err);
-}
-
-template <int MP, int NB>
-int launch_jl_nl(const fgx::DevCfg& c, const fgx::DevState& s, const float* params, const fgx::Outputs& o,
-                 hipStream_t stream, std::string& err) {
-  // the helper form (a joint wave and a helper wave per workgroup, FGX_JL_HELPER=1 / 2) measured slower
-  // at every shard size and was removed: asking for it is an error, not the plain form
-  if (const char* v = std::getenv("FGX_JL_HELPER"))
-    if (v[0] == '1' || v[0] == '2') {
-      err = "k_episode_jl: FGX_JL_HELPER asks for the helper form, which was removed (DESIGN.md 4.6a)";
-      return -4;
-    }
-  if (c.nl == 2) return launch_jl<MP, 2, NB>(c, s, params, o, stream, err);
-  if (c.nl == 5) return launch_jl<MP, 5, NB>(c, s, params, o, stream, err);
-  err = "k_episode_jl: n_links not instantiated (supported: 2, 5)";
-  return -4;
-}
-
-template <int NB>
-int launch_jl_mp(const fgx::DevCfg& c, const fgx::DevState& s, int mp, const float* params, const fgx::Outputs& o,
-                 hipStream_t stream, std::string& err) {
-  switch (mp) {
-    case fgx::MP_PROMP: return launch_jl_nl<fgx::MP_PROMP, NB>(c, s, params, o, stream, err);
-    case fgx::MP_DMP: return launch_jl_nl<fgx::MP_DMP, NB>(c, s, params, o, stream, err);
-    case fgx::MP_PRODMP: return launch_jl_nl<fgx::MP_PRODMP, NB>(c, s, params, o, stream, err);
-  }
-  err = "k_episode_jl: bad mp kind";
-  return -1;
+  return fgx::launch("k_episode_jl launch", fgx::k_episode_jl<MP, NL, NB>, dim3(blocks), dim3(S::THREADS + 64 * rw),
+                     S::lds_bytes(), stream, err, c, s, params, o, gw, rw);
 }
 }  // namespace
 
 int fgx_launch_episode_jl(const fgx::DevCfg& c, const fgx::DevState& s, int mp, int nbs, const float* params,
                           const fgx::Outputs& o, hipStream_t stream, std::string& err) {
-  if (nbs == 5) return launch_jl_mp<5>(c, s, mp, params, o, stream, err);
-  if (nbs == 0) return launch_jl_mp<0>(c, s, mp, params, o, stream, err);
-  err = "k_episode_jl: basis count not instantiated";
-  return -4;
+  using namespace fgx;
+  return pick<5, 0>(nbs, -4, "k_episode_jl: basis count not instantiated", err, [&](auto NB) {
+    return pick<MP_PROMP, MP_DMP, MP_PRODMP>(mp, -1, "k_episode_jl: bad mp kind", err, [&](auto MP) {
+      // the helper form (a joint wave and a helper wave per workgroup, FGX_JL_HELPER=1 / 2) measured slower
+      // at every shard size and was removed: asking for it is an error, not the plain form
+      if (const char* v = std::getenv("FGX_JL_HELPER"))
+        if (v[0] == '1' || v[0] == '2') {
+          err = "k_episode_jl: FGX_JL_HELPER asks for the helper form, which was removed (DESIGN.md 4.6a)";
+          return -4;
+        }
+      return pick<2, 5>(c.nl, -4, "k_episode_jl: n_links not instantiated (supported: 2, 5)", err, [&](auto NL) {
+        return launch_jl<MP, NL, NB>(c, s, params, o, stream, err);
+      });
+    });
+  });
 }

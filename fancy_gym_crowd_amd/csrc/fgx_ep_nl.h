@@ -48,11 +48,9 @@ int nl_episode(const DevCfg& c, const DevState& s, int mp, int kernel, const flo
                                                                          stream, err);
     }
   } else {
-    switch (c.env) {
-      case ENV_SIMPLE: return launch_episode_env<ENV_SIMPLE, 0, NL>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
-      case ENV_HOLE: return launch_episode_env<ENV_HOLE, 0, NL>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
-      case ENV_VIA: return launch_episode_env<ENV_VIA, 0, NL>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
-    }
+    return pick<ENV_SIMPLE, ENV_HOLE, ENV_VIA>(c.env, -1, "bad env kind", err, [&](auto ENV) {
+      return launch_episode_env<ENV, 0, NL>(c, s, mp, kernel, params, dpos, dvel, o, stream, err);
+    });
   }
   err = "bad env kind";
   return -1;
@@ -62,9 +60,8 @@ template <int NL>
 int nl_reset(const DevCfg& c, const DevState& s, const uint64_t* seeds, const uint8_t* mask, int rs_mode, float* obs,
              hipStream_t stream, std::string& err) {
   const int threads = 256;
-  hipLaunchKernelGGL((k_reset<NL>), dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s,
-                     seeds, mask, rs_mode, obs);
-  return launch_status("k_reset", err);
+  return launch("k_reset", k_reset<NL>, dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, err,
+                c, s, seeds, mask, rs_mode, obs);
 }
 
 template <int NL>
@@ -74,51 +71,44 @@ int nl_step_raw(const DevCfg& c, const DevState& s, const float* act, float* obs
   // LDS rows of the workgroup's action / observation slices (k_step_raw)
   const int so = step_raw_stride(c.obs_dim), sa = step_raw_stride(NL);
   const size_t lds = sizeof(float) * kStepRawBlock * ((so > sa ? so : sa) + (final_obs ? so : 0));
-  const auto k = c.env == ENV_SIMPLE ? k_step_raw<ENV_SIMPLE, NL>
-                 : c.env == ENV_HOLE ? k_step_raw<ENV_HOLE, NL>
-                                     : k_step_raw<ENV_VIA, NL>;
-  hipLaunchKernelGGL(k, grid, block, lds, stream, c, s, act, obs, rew, term, trunc, final_obs, autoreset);
-  return launch_status("k_step_raw", err);
+  return pick<ENV_SIMPLE, ENV_HOLE, ENV_VIA>(c.env, -1, "bad env kind", err, [&](auto ENV) {
+    return launch("k_step_raw", k_step_raw<ENV, NL>, grid, block, lds, stream, err, c, s, act, obs, rew, term, trunc,
+                  final_obs, autoreset);
+  });
 }
 
-// K<MP, NL, NB> of the handle's MP kind and basis count (one function type per K); null: no MP
-#define FGX_NL_KERNEL_MP(K, NB) \
-  (c.mp == MP_PROMP ? K<MP_PROMP, NL, NB> : c.mp == MP_DMP ? K<MP_DMP, NL, NB> : c.mp == MP_PRODMP ? K<MP_PRODMP, NL, NB> : nullptr)
-#define FGX_NL_KERNEL(K) (c.nb == kNB5<NL> ? FGX_NL_KERNEL_MP(K, kNB5<NL>) : FGX_NL_KERNEL_MP(K, 0))
+// f(MP, NB): the tags of the handle's MP kind and of the compiled basis count that serves c.nb
+// (kNB5<NL>, else the generic 0); no MP: -1 with `miss`
+template <int NL, class F>
+int pick_mp_nb(const DevCfg& c, const char* miss, std::string& err, F&& f) {
+  return pick<MP_PROMP, MP_DMP, MP_PRODMP>(c.mp, -1, miss, err, [&](auto MP) {
+    return pick<kNB5<NL>, 0>(c.nb == kNB5<NL> ? c.nb : 0, -1, miss, err, [&](auto NB) { return f(MP, NB); });
+  });
+}
 
 // k_traj_mfma (2 / 5 links), else k_traj_run, else k_traj_valu: the first that takes the plan
 template <int NL>
 int nl_traj(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel, hipStream_t stream,
             std::string& err) {
-  const auto valu = FGX_NL_KERNEL(k_traj_valu);
-  if (!valu) {
-    err = "step-based handle has no trajectory generator";
-    return -1;
-  }
-  if constexpr (kRegistered<NL>)
-    if (const int rm = launch_traj_mfma<NL>(c, s, params, dpos, dvel, stream, err); rm != 1) return rm;
-  if (const int rr = launch_traj_run<NL>(c, s, params, dpos, dvel, stream, err); rr != 1) return rr;
-  const int threads = 256;
-  hipLaunchKernelGGL(valu, dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s, params, dpos,
-                     dvel);
-  return launch_status("k_traj_valu", err);
+  return pick_mp_nb<NL>(c, "step-based handle has no trajectory generator", err, [&](auto MP, auto NB) {
+    if constexpr (kRegistered<NL>)
+      if (const int rm = launch_traj_mfma<NL>(c, s, params, dpos, dvel, stream, err); rm != 1) return rm;
+    if (const int rr = launch_traj_run<NL>(c, s, params, dpos, dvel, stream, err); rr != 1) return rr;
+    const int threads = 256;
+    return launch("k_traj_valu", k_traj_valu<MP, NL, NB>, dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads),
+                  0, stream, err, c, s, params, dpos, dvel);
+  });
 }
 
 template <int NL>
 int nl_traj_env(const DevCfg& c, const DevState& s, const float* params, float* env_tab, float* dpos, float* dvel,
                 int32_t* plan_len, float* info_pos, float* info_vel, hipStream_t stream, std::string& err) {
-  const auto k = FGX_NL_KERNEL(k_traj_env);
-  if (!k) {
-    err = "learned phase parameters need a movement primitive";
-    return -1;
-  }
-  const int threads = 256;
-  hipLaunchKernelGGL(k, dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0, stream, c, s, params, env_tab,
-                     dpos, dvel, plan_len, info_pos, info_vel);
-  return launch_status("k_traj_env", err);
+  return pick_mp_nb<NL>(c, "learned phase parameters need a movement primitive", err, [&](auto MP, auto NB) {
+    const int threads = 256;
+    return launch("k_traj_env", k_traj_env<MP, NL, NB>, dim3((unsigned)((c.N + threads - 1) / threads)), dim3(threads), 0,
+                  stream, err, c, s, params, env_tab, dpos, dvel, plan_len, info_pos, info_vel);
+  });
 }
-#undef FGX_NL_KERNEL
-#undef FGX_NL_KERNEL_MP
 }  // namespace
 
 const fgx::NlOps* FGX_NL_CAT(fgx_nl_ops_, FGX_NL)() {

@@ -1,10 +1,27 @@
-// fgx_launch.h — the launch functions the translation units offer each other: declarations only, so
-// the C ABI unit (fgx_api.hip) reaches every kernel family without seeing a kernel template.
+// fgx_launch.h — how every unit gets from run-time kinds to a launched kernel, and what the units
+// offer each other.  The rule a kernel family follows: pick<...> each run-time kind into a template
+// argument (nested, `if constexpr` on the tags for what the unit does not instantiate), then launch(...)
+// (fgx_device.h) with the family's grid, block and LDS size.  The declarations below are functions
+// only, so the C ABI unit (fgx_api.hip) reaches every kernel family without seeing a kernel template.
 // All return 0 or an FGX_E_* code (-1 bad kind / no MP, -2 HIP error, -4 not instantiated), message in err.
 #pragma once
 #include <string>
+#include <type_traits>
 
 #include "fgx_device.h"
+
+namespace fgx {
+// Calls f(std::integral_constant<int, V>{}) for the first listed V that equals v and returns its
+// result; no V equals v: f is not called, err = miss, returns miss_code.  (A bool: pick<0, 1>.)
+template <int... Vs, class F>
+int pick(int v, int miss_code, const char* miss, std::string& err, F&& f) {
+  int rc = miss_code;
+  bool hit = false;
+  ((v == Vs && !hit ? (hit = true, rc = f(std::integral_constant<int, Vs>{}), 0) : 0), ...);
+  if (!hit) err = miss;
+  return rc;
+}
+}  // namespace fgx
 
 // k_episode and its variants per env kind (fgx_ep_<env>.hip: NB = 5; fgx_ep_<env>_gen.hip: NB = 0), 2 / 5
 // links; kernel: the EK_* id select_episode_kernel chose (fgx_select.h)

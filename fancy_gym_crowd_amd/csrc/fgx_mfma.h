@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "fgx_kernels.h"
+#include "fgx_launch.h"
 
 namespace fgx {
 
@@ -463,13 +464,6 @@ __global__ __launch_bounds__(64 * kTrajGWaves) void k_traj_mfma(DevCfg c, DevSta
   }
 }
 
-// a launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first
-template <typename F>
-inline void launch_lds(const void* kernel, size_t lds, F&& launch) {
-  (void)raise_lds_limit(kernel, lds);
-  launch();
-}
-
 // 0: launched; 1: not applicable (the caller goes on to k_traj_run); -2: launch error, message in err
 template <int NL>
 inline int launch_traj_mfma(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel,
@@ -482,9 +476,9 @@ inline int launch_traj_mfma(const DevCfg& c, const DevState& s, const float* par
   if (r3) {
     const int64_t groups = (c.N + 31) / 32;
     const dim3 grid((unsigned)((groups + kTrajWaves - 1) / kTrajWaves)), block(64 * kTrajWaves);
-    if (c.mp == MP_PROMP) hipLaunchKernelGGL((k_traj_mfma_r3<MP_PROMP, NL>), grid, block, 0, stream, c, s, params, dpos, dvel);
-    else hipLaunchKernelGGL((k_traj_mfma_r3<MP_PRODMP, NL>), grid, block, 0, stream, c, s, params, dpos, dvel);
-    return launch_status("k_traj_mfma_r3", err);
+    return pick<MP_PROMP, MP_PRODMP>(c.mp, 1, "k_traj_mfma_r3: ProMP / ProDMP only", err, [&](auto MP) {
+      return launch("k_traj_mfma_r3", k_traj_mfma_r3<MP, NL>, grid, block, 0, stream, err, c, s, params, dpos, dvel);
+    });
   }
   const size_t lds = traj_mfma_lds_bytes(c.rows, c.stride, c.T, c.mp, c.nl);
   if (lds > 160 * 1024) return 1;   // (a table this long: the VALU kernel)
@@ -493,11 +487,9 @@ inline int launch_traj_mfma(const DevCfg& c, const DevState& s, const float* par
   int blocks = (int)std::min<int64_t>(groups, 256);
   if (const char* gv = std::getenv("FGX_TRAJ_GRID")) blocks = (int)std::max<int64_t>(1, std::min<int64_t>(groups, std::atoll(gv)));
   const dim3 grid(blocks), block(64 * kTrajGWaves);
-  if (c.mp == MP_PROMP)
-    launch_lds((const void*)k_traj_mfma<MP_PROMP, NL>, lds, [&] { hipLaunchKernelGGL((k_traj_mfma<MP_PROMP, NL>), grid, block, lds, stream, c, s, params, dpos, dvel); });
-  else
-    launch_lds((const void*)k_traj_mfma<MP_PRODMP, NL>, lds, [&] { hipLaunchKernelGGL((k_traj_mfma<MP_PRODMP, NL>), grid, block, lds, stream, c, s, params, dpos, dvel); });
-  return launch_status("k_traj_mfma", err);
+  return pick<MP_PROMP, MP_PRODMP>(c.mp, 1, "k_traj_mfma: ProMP / ProDMP only", err, [&](auto MP) {
+    return launch("k_traj_mfma", k_traj_mfma<MP, NL>, grid, block, lds, stream, err, c, s, params, dpos, dvel);
+  });
 }
 
 }  // namespace fgx

@@ -314,23 +314,15 @@ inline int launch_traj_run(const DevCfg& c, const DevState& s, const float* para
   const int nt = sh.nt;
   const int blocks = (int)std::min<int64_t>(groups, (int64_t)device_cus() * sh.per_cu);
   const dim3 grid(blocks), block(sh.threads);
-#define RUN(MPV, NBV, V4V)                                                                                      \
-  launch_lds((const void*)k_traj_run<MPV, NL, NBV, V4V>, sh.lds, [&] {                                        \
-    hipLaunchKernelGGL((k_traj_run<MPV, NL, NBV, V4V>), grid, block, sh.lds, stream, c, s, params, dpos, dvel, \
-                       sh.GE, sh.RC, nt, sh.sep);                                                             \
-  })
-#define BY_V4(MPV, NBV) \
-  if (v4) RUN(MPV, NBV, true); else RUN(MPV, NBV, false)
-#define BY_NB(MPV) \
-  if (c.nb == 5) { BY_V4(MPV, 5); } else { BY_V4(MPV, 0); }
-  if (c.mp == MP_PROMP) { BY_NB(MP_PROMP) }
-  else if (c.mp == MP_DMP) { BY_NB(MP_DMP) }
-  else if (c.mp == MP_PRODMP) { BY_NB(MP_PRODMP) }
-  else return 1;
-#undef BY_NB
-#undef BY_V4
-#undef RUN
-  return launch_status("k_traj_run", err);
+  const char* const no_mp = "k_traj_run: no movement primitive";   // (1: not applicable)
+  return pick<MP_PROMP, MP_DMP, MP_PRODMP>(c.mp, 1, no_mp, err, [&](auto MP) {
+    return pick<5, 0>(c.nb == 5 ? 5 : 0, 1, no_mp, err, [&](auto NB) {
+      return pick<0, 1>(v4, 1, no_mp, err, [&](auto V4) {
+        return launch("k_traj_run", k_traj_run<MP, NL, NB, V4 != 0>, grid, block, sh.lds, stream, err, c, s, params, dpos,
+                      dvel, sh.GE, sh.RC, nt, sh.sep);
+      });
+    });
+  });
 }
 
 }  // namespace fgx
