@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libfgx.so")
 
-FGX_ABI_VERSION = 8
+FGX_ABI_VERSION = 9
 INNER_STEPS_LEN = 128 * 16   # include/fgx.h FGX_INNER_STEPS_LEN (partial counters, sum them)
 ENV_SIMPLE, ENV_HOLE, ENV_VIA = 0, 1, 2
 REW_SIMPLE, REW_VEL_ACC, REW_UNBOUNDED = 0, 1, 2
@@ -80,6 +80,12 @@ EXPORTS = {
     "fgx_step_raw": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int32, ctypes.c_void_p]),
     "fgx_get_state": (ctypes.c_int, [ctypes.c_void_p] * 7),
     "fgx_set_state": (ctypes.c_int, [ctypes.c_void_p] * 7),
+    # ---- ABI 9: complete snapshots
+    "fgx_snapshot_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    "fgx_snapshot": (ctypes.c_int, [ctypes.c_void_p] * 3),
+    "fgx_restore": (ctypes.c_int, [ctypes.c_void_p] * 3),
+    "fgx_fingerprint": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "fgx_copy_envs": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]),
     "fgx_get_tables": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "fgx_episode_kernel": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "fgx_selftest_sincos": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),

@@ -15,6 +15,7 @@
 #include "fgx_kernels.h"
 #include "fgx_launch.h"
 #include "fgx_select.h"
+#include "fgx_snapshot.h"
 #include "fgx_tables_k.h"
 
 using namespace fgx;
@@ -52,10 +53,25 @@ struct Handle {
   int32_t* plan_len = nullptr;
   void* learned_block = nullptr;
   double* obs_scratch = nullptr;   // info_level 2, SimpleReacher: qlog [T][nl][N] + gsave [2][N]
+  uint64_t fingerprint = 0;        // fgx_fingerprint: which handles and blobs hold interchangeable envs
   bool learned() const { return dc.learn_tau || dc.learn_delay; }
 };
 
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+static_assert(kSnapAlign == 256, "a blob section is padded like a section of the state block (fgx_snapshot.h)");
+
+// FNV-1a over the resolved configuration (every fgx_config field the engine reads, as build_devcfg
+// flattened it into a zero-filled DevCfg: no padding bytes of the caller's struct), without the env count
+uint64_t hash_config(const DevCfg& dc) {
+  DevCfg d;
+  std::memcpy(&d, &dc, sizeof(d));   // (padding included: build_devcfg zero-fills before it assigns)
+  d.N = 0;
+  d.wbound32 = 0.0f;   // (a function of the tables, set after they are built)
+  uint64_t x = 0xcbf29ce484222325ull ^ (uint64_t)FGX_ABI_VERSION;
+  const unsigned char* b = (const unsigned char*)&d;
+  for (size_t i = 0; i < sizeof(d); ++i) x = (x ^ b[i]) * 0x100000001b3ull;
+  return x;
+}
 
 }  // namespace
 
@@ -316,6 +332,7 @@ int fgx_create(const fgx_config* cfg, int64_t n_envs, int device, void** handle)
   h->device = device;
   int rc = build_devcfg(*cfg, n_envs, h->dc, h->ctx_dim);
   if (rc) { delete h; return rc; }
+  h->fingerprint = hash_config(h->dc);
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) { delete h; return fail(FGX_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)); }
   const int64_t N = n_envs;
@@ -634,6 +651,47 @@ int fgx_set_state(void* handle, const double* q, const double* qd, const double*
   Handle* h = (Handle*)handle;
   if (!h) return fail(FGX_E_INVALID, "null handle");
   return fgx_untranspose_state(h->dc, h->st, q, qd, goal, hole, steps, (hipStream_t)stream, g_err);
+}
+
+int fgx_snapshot_bytes(void* handle, int64_t* bytes) {
+  Handle* h = (Handle*)handle;
+  if (!h || !bytes) return fail(FGX_E_INVALID, "null argument");
+  *bytes = (int64_t)snapshot_layout(h->dc, h->st).bytes;
+  return FGX_OK;
+}
+
+int fgx_snapshot(void* handle, void* blob, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h || !blob) return fail(FGX_E_INVALID, "null argument");
+  if ((uintptr_t)blob & 15) return fail(FGX_E_INVALID, "blob must be 16-byte aligned");
+  return snapshot_launch(h->dc, h->st, (char*)blob, true, (hipStream_t)stream, g_err);
+}
+
+int fgx_restore(void* handle, const void* blob, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h || !blob) return fail(FGX_E_INVALID, "null argument");
+  if ((uintptr_t)blob & 15) return fail(FGX_E_INVALID, "blob must be 16-byte aligned");
+  return snapshot_launch(h->dc, h->st, (char*)blob, false, (hipStream_t)stream, g_err);
+}
+
+int fgx_fingerprint(void* handle, uint64_t* config_hash) {
+  Handle* h = (Handle*)handle;
+  if (!h || !config_hash) return fail(FGX_E_INVALID, "null argument");
+  *config_hash = h->fingerprint;
+  return FGX_OK;
+}
+
+int fgx_copy_envs(void* dst, void* src, const int64_t* dst_idx, const int64_t* src_idx, int64_t m, void* stream) {
+  Handle* hd = (Handle*)dst;
+  Handle* hs = (Handle*)src;
+  if (!hd || !hs) return fail(FGX_E_INVALID, "null handle");
+  if (m < 0) return fail(FGX_E_INVALID, "m must be >= 0");
+  if (hd->device != hs->device) return fail(FGX_E_INVALID, "fgx_copy_envs: the handles are on different devices");
+  if (hd->fingerprint != hs->fingerprint)
+    return fail(FGX_E_INVALID, "fgx_copy_envs: the handles were created from different configurations");
+  if (m == 0) return FGX_OK;
+  if (!dst_idx || !src_idx) return fail(FGX_E_INVALID, "null index array");
+  return copy_envs_launch(hd->dc, hd->st, hs->dc, hs->st, dst_idx, src_idx, m, (hipStream_t)stream, g_err);
 }
 
 int fgx_get_tables(void* handle, float* out, void* stream) {

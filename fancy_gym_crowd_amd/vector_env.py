@@ -150,6 +150,7 @@ class BlackBoxVectorEnv:
         cfg, meta = resolve(env_id, mp_config_override, **env_kwargs)
         if meta["mp_type"] is None:
             raise ValueError(f"{env_id} is a step-based id; use StepVectorEnv / make()")
+        self.env_id = env_id
         self.meta = meta
         self.num_envs = int(num_envs)
         self.info_level = meta["verbose"] if info_level is None else int(info_level)
@@ -376,6 +377,30 @@ class BlackBoxVectorEnv:
         _lib.check(self._eng.lib.fgx_set_state(self._eng.h, _ptr(q), _ptr(qd), _ptr(goal), _ptr(hole), _ptr(steps),
                                                self._eng.stream()))
 
+    # ------------------------------------------------------------------ checkpoint / branching
+    def state_dict(self):
+        """The complete state of every env (fgx_snapshot: get_state()'s five arrays and the PCG64
+        streams, start angles, plan counters, conditions, flags and reward state), so that a run
+        continues from it bit for bit: {'format': 1, 'env_id', 'num_envs', 'fingerprint',
+        'needs_reset', 'blob': uint8 device tensor}.  torch.save works on it.  No host sync."""
+        return _state_dict(self)
+
+    def load_state_dict(self, sd):
+        """Restore a state_dict() of an env of the same configuration and num_envs (ValueError
+        otherwise, the env untouched).  The blob may be on the CPU or on any device.  A freshly
+        constructed env can be loaded and stepped without reset().  With the blob already on the
+        env's device: one kernel launch, no host sync, no allocation (HIP-graph capturable)."""
+        _load_state_dict(self, sd)
+
+    def copy_envs(self, src_idx, dst_idx, source=None, check=True):
+        """Env src_idx[j] of `source` (an env of the same configuration; None: this env) replaces
+        env dst_idx[j] of this env, random stream included: the copies continue identically and
+        draw the same future contexts (common random numbers).  src_idx may repeat (fan-out);
+        dst_idx must be distinct and, within one env, disjoint from src_idx.  check=True verifies
+        that and the index ranges (ValueError) at the cost of a host sync; check=False trusts the
+        caller (fgx_copy_envs skips out-of-range pairs; overlapping sets give undefined rows)."""
+        _copy_envs(self, src_idx, dst_idx, source, check)
+
     def episode_kernel(self, info_level=None):
         """Name of the HIP kernel step() launches (fgx_episode_kernel): k_episode, k_episode_jp,
         k_episode_ws, k_episode_jl, k_episode_w2, k_episode_pair, k_episode_v2, k_episode_v2h or k_episode_hp
@@ -411,6 +436,7 @@ class StepVectorEnv:
         cfg, meta = resolve(env_id, None, **env_kwargs)
         if meta["mp_type"] is not None:
             raise ValueError(f"{env_id} is a black-box id; use BlackBoxVectorEnv")
+        self.env_id = env_id
         self.meta = meta
         self.num_envs = int(num_envs)
         self.autoreset = bool(autoreset)
@@ -457,6 +483,18 @@ class StepVectorEnv:
     def set_state(self, q=None, qd=None, goal=None, hole=None, steps=None):
         """fgx_set_state (checkpoint restore / tests), as BlackBoxVectorEnv.set_state."""
         return BlackBoxVectorEnv.set_state(self, q, qd, goal, hole, steps)
+
+    def state_dict(self):
+        """As BlackBoxVectorEnv.state_dict."""
+        return _state_dict(self)
+
+    def load_state_dict(self, sd):
+        """As BlackBoxVectorEnv.load_state_dict."""
+        _load_state_dict(self, sd)
+
+    def copy_envs(self, src_idx, dst_idx, source=None, check=True):
+        """As BlackBoxVectorEnv.copy_envs."""
+        _copy_envs(self, src_idx, dst_idx, source, check)
 
     def close(self):
         self._eng.close()
@@ -519,6 +557,79 @@ def _reset_engine(env, seed, options, obs):
     rs = -1 if rs is None else int(bool(rs))
     _lib.check(env._eng.lib.fgx_reset(env._eng.h, _ptr(seeds), _ptr(mask), rs, _ptr(obs), env._eng.stream()))
     env._needs_reset = False
+
+
+STATE_FORMAT = 1   # state_dict()['format']: the blob layout of csrc/fgx_snapshot.h
+
+
+def _fingerprint(env):
+    fp = ctypes.c_uint64()
+    _lib.check(env._eng.lib.fgx_fingerprint(env._eng.h, ctypes.byref(fp)))
+    return int(fp.value)
+
+
+def _snapshot_bytes(env):
+    n = ctypes.c_int64()
+    _lib.check(env._eng.lib.fgx_snapshot_bytes(env._eng.h, ctypes.byref(n)))
+    return int(n.value)
+
+
+def _state_dict(env):
+    blob = torch.zeros(_snapshot_bytes(env), dtype=torch.uint8, device=env.device)
+    _lib.check(env._eng.lib.fgx_snapshot(env._eng.h, _ptr(blob), env._eng.stream()))
+    return {"format": STATE_FORMAT, "env_id": env.env_id, "num_envs": env.num_envs, "fingerprint": _fingerprint(env),
+            "needs_reset": bool(env._needs_reset), "blob": blob}
+
+
+def _load_state_dict(env, sd):
+    """Every check comes before the engine is touched (the C ABI cannot look into a device blob)."""
+    for k in ("format", "num_envs", "fingerprint", "needs_reset", "blob"):
+        if k not in sd:
+            raise ValueError(f"state_dict has no '{k}'")
+    if sd["format"] != STATE_FORMAT:
+        raise ValueError(f"state_dict format {sd['format']!r}; this build reads format {STATE_FORMAT}")
+    if int(sd["num_envs"]) != env.num_envs:
+        raise ValueError(f"state_dict of {sd['num_envs']} envs loaded into {env.num_envs}")
+    if int(sd["fingerprint"]) != _fingerprint(env):
+        raise ValueError(f"state_dict of another configuration ({sd.get('env_id')!r}, fingerprint "
+                         f"{int(sd['fingerprint']):#x}) loaded into {env.env_id!r} ({_fingerprint(env):#x})")
+    blob = sd["blob"]
+    nbytes = _snapshot_bytes(env)
+    if not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.dim() != 1 or blob.numel() != nbytes:
+        raise ValueError(f"state_dict blob must be a uint8 tensor of {nbytes} bytes")
+    blob = blob.to(env.device).contiguous()
+    if blob.data_ptr() % 16:
+        blob = blob.clone()
+    _lib.check(env._eng.lib.fgx_restore(env._eng.h, _ptr(blob), env._eng.stream()))
+    env._needs_reset = bool(sd["needs_reset"])
+
+
+def _copy_envs(env, src_idx, dst_idx, source, check):
+    src = env if source is None else source
+    if not isinstance(src, (BlackBoxVectorEnv, StepVectorEnv)):
+        raise ValueError("source must be a BlackBoxVectorEnv / StepVectorEnv")
+    if src.device != env.device:
+        raise ValueError(f"source is on {src.device}, this env on {env.device}")
+    if _fingerprint(src) != _fingerprint(env):
+        raise ValueError(f"source ({src.env_id!r}) has another configuration than this env ({env.env_id!r})")
+    s = torch.as_tensor(src_idx, device=env.device).to(torch.int64).reshape(-1).contiguous()
+    d = torch.as_tensor(dst_idx, device=env.device).to(torch.int64).reshape(-1).contiguous()
+    if s.numel() != d.numel():
+        raise ValueError(f"{s.numel()} source indices for {d.numel()} destinations")
+    if s.numel() == 0:
+        return
+    if check:   # (one host sync)
+        never = torch.zeros((), dtype=torch.bool, device=env.device)
+        bad = torch.stack([((s < 0) | (s >= src.num_envs)).any(), ((d < 0) | (d >= env.num_envs)).any(),
+                           (torch.sort(d).values.diff() == 0).any(),
+                           torch.isin(d, s).any() if src is env else never]).cpu().tolist()
+        if bad[0] or bad[1]:
+            raise ValueError("copy_envs: index out of range")
+        if bad[2]:
+            raise ValueError("copy_envs: dst_idx repeats an env")
+        if bad[3]:
+            raise ValueError("copy_envs: within one env src_idx and dst_idx must be disjoint")
+    _lib.check(env._eng.lib.fgx_copy_envs(env._eng.h, src._eng.h, _ptr(d), _ptr(s), int(s.numel()), env._eng.stream()))
 
 
 def math_isnan(x):

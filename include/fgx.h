@@ -21,7 +21,10 @@
  *   fgx_step_raw      step-based env.step(action) (+ autoreset)         base_reacher/base_reacher_torque.py:20-37,
  *                                                                       base_reacher/base_reacher_direct.py:20-38
  *   fgx_get_state /   env.unwrapped.current_pos/current_vel, goal, hole black_box/raw_interface_wrapper.py:24-44
- *   fgx_set_state     (checkpoint/test access)
+ *   fgx_set_state     (test access; five of the eleven state arrays)
+ *   fgx_snapshot /    the complete state of every env: bit-exact resume        (no counterpart: deepcopy /
+ *   fgx_restore /     and branching (common random numbers)                     pickle of the env objects)
+ *   fgx_copy_envs
  *   fgx_get_tables    basis tables (test/introspection)
  *   fgx_episode_kernel which episode kernel fgx_step launches (introspection / benchmarks)
  *
@@ -46,7 +49,7 @@
 extern "C" {
 #endif
 
-#define FGX_ABI_VERSION 8
+#define FGX_ABI_VERSION 9
 
 /* error codes */
 #define FGX_OK 0
@@ -258,6 +261,36 @@ int fgx_get_state(void* handle, double* q, double* qd, double* goal, double* hol
                   void* stream);
 int fgx_set_state(void* handle, const double* q, const double* qd, const double* goal,
                   const double* hole, const int32_t* steps, void* stream);
+
+/* ---- ABI 9: complete snapshots.  fgx_get_state / fgx_set_state move q, qd, goal, hole and steps;
+ * a handle keeps six more arrays between calls (each env's PCG64 stream, last start angle,
+ * plan_steps, condition_on_desired state, flags, HoleReacher reward state).  A snapshot is all
+ * eleven in one device blob of fgx_snapshot_bytes bytes: the arrays as the handle holds them
+ * ([rows][N], env index innermost), in the order q, qd, goal, hole, reward state, steps, plan_steps,
+ * flags, rng, condition, start angle, each starting on a 256-byte boundary, no header (the reward
+ * state and the condition only where the handle allocates them).  A handle holds no host-side
+ * state that changes between calls, so restoring a blob continues the run bit for bit: the same
+ * auto-reset draws, the same replanning counters.
+ * blob: a device pointer on the handle's device, 16-byte aligned.  fgx_snapshot and fgx_restore
+ * are one kernel launch each, stream-ordered, without host synchronisation or allocation (they can
+ * be captured in a HIP graph).  fgx_restore cannot look into a device blob without synchronising:
+ * THE CALLER pairs every blob with the fingerprint and n_envs of the handle it was taken from and
+ * restores it only into a handle with the same two values (the Python layer's state_dict does). */
+int fgx_snapshot_bytes(void* handle, int64_t* bytes);
+int fgx_snapshot(void* handle, void* blob, void* stream);
+int fgx_restore(void* handle, const void* blob, void* stream);
+/* config_hash (a host value): a hash of the configuration the handle was created from, as
+ * fgx_create resolved it (every fgx_config field the engine reads; not of n_envs).  Handles with
+ * equal fingerprints hold interchangeable envs. */
+int fgx_fingerprint(void* handle, uint64_t* config_hash);
+/* For j < m: the complete state of env src_idx[j] of `src` (its random stream included) replaces
+ * env dst_idx[j] of `dst`; dst_idx, src_idx: device int64 [m].  src_idx may repeat (fan-out: many
+ * envs continue from one state and draw the same future contexts).  THE CALLER guarantees that
+ * dst_idx holds distinct envs and, when dst == src, that no env is in both index sets; the copy is
+ * one pass and its result is undefined otherwise.  A pair with an index outside [0, n_envs) of its
+ * handle is skipped.  FGX_E_INVALID for handles on different devices or with different
+ * fingerprints; m == 0 is a no-op.  One launch, stream-ordered, no host synchronisation. */
+int fgx_copy_envs(void* dst, void* src, const int64_t* dst_idx, const int64_t* src_idx, int64_t m, void* stream);
 
 /* Copy the f32 basis tables [table_rows, table_stride] to out (device). */
 int fgx_get_tables(void* handle, float* out, void* stream);
