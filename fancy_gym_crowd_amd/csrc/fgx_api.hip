@@ -54,7 +54,12 @@ struct Handle {
   void* learned_block = nullptr;
   double* obs_scratch = nullptr;   // info_level 2, SimpleReacher: qlog [T][nl][N] + gsave [2][N]
   uint64_t fingerprint = 0;        // fgx_fingerprint: which handles and blobs hold interchangeable envs
+  // wide handle (n_basis > 12, or FGX_WIDE=1 at fgx_create): k_traj_wide plans into plan_pos / plan_vel
+  // and the episode runs over them as given plans
+  bool wide = false;
   bool learned() const { return dc.learn_tau || dc.learn_delay; }
+  // the MP kind the episode kernel sees: MP_GIVEN for per-env (learned) and wide plans
+  int episode_mp() const { return learned() || wide ? (int)MP_GIVEN : dc.mp; }
 };
 
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
@@ -93,6 +98,20 @@ static int select_kernel(const Handle& h, int mp, const Outputs& o, bool per_env
       KernelOverrides::from_env());
 }
 
+// What k_traj_wide serves (the set k_traj_mfma serves): ProMP / ProDMP plans that all start on table row
+// 0.  Null, or the part of the configuration that keeps the handle off the wide path.
+static const char* wide_obstacle(const fgx_config& c) {
+  if (c.mp_kind == FGX_MP_DMP) return "DMP";
+  if (c.mp_kind != FGX_MP_PROMP && c.mp_kind != FGX_MP_PRODMP) return "no movement primitive";
+  if (c.replan_period > 0 || c.sched_n > 0) return "a replanning schedule";
+  if (c.learn_tau) return "learn_tau";
+  if (c.learn_delay) return "learn_delay";
+  if (c.learn_sub_trajectories) return "learn_sub_trajectories";
+  if (c.condition_on_desired) return "condition_on_desired";
+  return nullptr;
+}
+constexpr int kWideBasis = 1024;   // n_basis + zero_start + zero_goal of a wide handle (include/fgx.h)
+
 // ------------------------------------------------------------------------ config -> DevCfg
 static int build_devcfg(const fgx_config& c, int64_t N, DevCfg& d, int& ctx_dim) {
   if (c.abi_version != FGX_ABI_VERSION) return fail(FGX_E_INVALID, "abi_version mismatch");
@@ -128,8 +147,21 @@ static int build_devcfg(const fgx_config& c, int64_t N, DevCfg& d, int& ctx_dim)
     if (c.T <= 0) return fail(FGX_E_INVALID, "T must be positive");
     // the in-register return sum restates numpy's pairwise summation with one recursion level
     if (c.T > 256) return fail(FGX_E_UNSUPPORTED, "plan length T > 256 not supported");
-    if (c.n_basis < 1 || c.n_basis > kGenBasis) return fail(FGX_E_UNSUPPORTED, "n_basis must be in [1, 12]");
-    if (c.n_basis + c.zero_start + c.zero_goal > kMaxBasis) return fail(FGX_E_INVALID, "too many basis functions");
+    if (c.n_basis < 1) return fail(FGX_E_UNSUPPORTED, "n_basis must be at least 1");
+    if (c.zero_start < 0 || c.zero_goal < 0) return fail(FGX_E_INVALID, "zero padding counts must be >= 0");
+    if (c.n_basis > kGenBasis) {   // the wide path (k_traj_wide) or nothing
+      const int n = c.n_basis + c.zero_start + c.zero_goal;
+      if (c.n_basis > kWideBasis || n > kWideBasis)
+        return fail(FGX_E_UNSUPPORTED, "n_basis " + std::to_string(c.n_basis) + " with " +
+                                           std::to_string(n - c.n_basis) + " zero-padding bases: n_basis + zero_start + "
+                                           "zero_goal must be <= 1024");
+      if (const char* why = wide_obstacle(c))
+        return fail(FGX_E_UNSUPPORTED, "n_basis " + std::to_string(c.n_basis) + " with " + why +
+                                           " is not supported: n_basis > 12 serves ProMP / ProDMP without replanning, "
+                                           "learned phase parameters or condition_on_desired");
+    } else if (c.n_basis + c.zero_start + c.zero_goal > kMaxBasis) {
+      return fail(FGX_E_INVALID, "too many basis functions");
+    }
     // centres (j - o) / (n - 2o - 1) of the unbounded phase (fgx_tables.h rbf64): n - 2o - 1 >= 1
     if (c.num_basis_outside < 0 || c.n_basis + c.zero_start + c.zero_goal - 2 * c.num_basis_outside - 1 < 1)
       return fail(FGX_E_INVALID, "num_basis_outside must satisfy 0 <= o and num_basis - 2 o > 1");
@@ -223,7 +255,8 @@ static int build_devcfg(const fgx_config& c, int64_t N, DevCfg& d, int& ctx_dim)
     d.stride = (c.n_basis + 2 + 3) & ~3;   // [basis..., dt32 | sdt, rcp(dt32), pad] (16-B rows)
   }
   if (c.mp_kind == FGX_MP_NONE) { d.rows = 0; d.stride = 0; }
-  if ((int64_t)d.rows * d.stride * 4 > 64 * 1024)
+  // (a handle with n_basis > 12 is wide: nothing stages its table whole into LDS)
+  if (c.n_basis <= kGenBasis && (int64_t)d.rows * d.stride * 4 > 64 * 1024)
     return fail(FGX_E_UNSUPPORTED, "MP tables exceed 64 KiB of LDS (episode / replanning too long)");
   d.rand_width = std::isnan(c.hole_width);
   d.rand_x = std::isnan(c.hole_x);
@@ -333,6 +366,15 @@ int fgx_create(const fgx_config* cfg, int64_t n_envs, int device, void** handle)
   int rc = build_devcfg(*cfg, n_envs, h->dc, h->ctx_dim);
   if (rc) { delete h; return rc; }
   h->fingerprint = hash_config(h->dc);
+  h->wide = cfg->mp_kind != FGX_MP_NONE && !wide_obstacle(*cfg) &&
+            (cfg->n_basis > kGenBasis || KernelOverrides::from_env().wide);
+  if (h->wide) {
+    if (const char* why = fgx_traj_wide_refusal(h->dc)) {
+      const std::string msg = std::string("k_traj_wide: ") + why;
+      delete h;
+      return fail(FGX_E_UNSUPPORTED, msg);
+    }
+  }
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) { delete h; return fail(FGX_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)); }
   const int64_t N = n_envs;
@@ -393,18 +435,29 @@ int fgx_create(const fgx_config* cfg, int64_t n_envs, int device, void** handle)
     h->plan_vel = (float*)(lb + o_pv);
     h->plan_len = (int32_t*)(lb + o_pl);
   }
-  // basis tables
+  if (h->wide) {   // the plans k_traj_wide writes and the episode reads, [N, T, dof] f32 each
+    const size_t pb = align_up(sizeof(float) * (size_t)N * h->dc.T * nl);
+    e = hipMalloc(&h->learned_block, 2 * pb);
+    if (e != hipSuccess) { fgx_destroy(h); return fail(FGX_E_NOMEM, "hipMalloc wide plans"); }
+    h->plan_pos = (float*)h->learned_block;
+    h->plan_vel = (float*)((char*)h->learned_block + pb);
+  }
+  // basis tables (scratch: the rows' exponentials, then for ProDMP the fine grid's integrals)
   const DevCfg& d = h->dc;
+  const int nexp = d.nb + d.zs + d.zg;
   if (d.mp == MP_PROMP || d.mp == MP_DMP) {
     const int thr = 128, blk = (d.rows + thr - 1) / thr;
+    e = hipMalloc(&h->scratch, sizeof(double) * tables_exp_scratch(blk * thr, nexp) + 64);
+    if (e != hipSuccess) { fgx_destroy(h); return fail(FGX_E_NOMEM, "hipMalloc scratch"); }
     hipLaunchKernelGGL(k_tables_rbf, dim3(blk), dim3(thr), 0, 0, d, cfg->tau, cfg->delay, cfg->alpha_phase,
-                       cfg->bandwidth, h->tables);
+                       cfg->bandwidth, h->scratch, h->tables);
   } else if (d.mp == MP_PRODMP) {
     const int Rf = prodmp_fine_rows(d.dt, d.bdt, d.rows, cfg->tau, cfg->delay);   // fine-grid rows
-    e = hipMalloc(&h->scratch, sizeof(double) * (size_t)Rf * 2 * d.nb + 64);
+    const size_t nes = (tables_exp_scratch(256, nexp) + 7) & ~size_t(7);
+    e = hipMalloc(&h->scratch, sizeof(double) * (nes + (size_t)Rf * 2 * d.nb) + 64);
     if (e != hipSuccess) { fgx_destroy(h); return fail(FGX_E_NOMEM, "hipMalloc scratch"); }
     hipLaunchKernelGGL(k_tables_prodmp, dim3(1), dim3(256), 0, 0, d, cfg->tau, cfg->delay, cfg->alpha_phase,
-                       cfg->bandwidth, Rf, h->scratch, h->tables);
+                       cfg->bandwidth, Rf, h->scratch + nes, h->scratch, h->tables);
   }
   if (d.mp != MP_NONE && d.rows > 0) {
     const int n = tables_t_rows(d.rows) * d.stride;
@@ -574,11 +627,11 @@ int fgx_step(void* handle, const float* params, float* obs, double* ret, uint8_t
     return fail(FGX_E_INVALID, "reward_dist and reward_ctrl must be given together");
   if (info_too_large(h, info)) return fail(FGX_E_UNSUPPORTED, "per-step info arrays need n_envs < 2^24");
   Outputs o = make_outputs(obs, ret, terminated, truncated, traj_len, final_obs, info, autoreset);
-  if (h->learned()) {   // k_traj_env writes the planned positions / velocities, not the episode kernel
+  if (h->learned() || h->wide) {   // k_traj_env / k_traj_wide writes the planned positions / velocities, not the episode kernel
     o.positions = nullptr;
     o.velocities = nullptr;
   }
-  const int kernel = select_kernel(*h, h->learned() ? MP_GIVEN : h->dc.mp, o, h->learned());
+  const int kernel = select_kernel(*h, h->episode_mp(), o, h->learned());
   if (const int rc = attach_obs_scratch(h, o, kernel, (hipStream_t)stream)) return rc;
   const NlOps& ops = nl_ops(h->dc.nl);
   if (h->learned()) {
@@ -593,6 +646,18 @@ int fgx_step(void* handle, const float* params, float* obs, double* ret, uint8_t
     st.plan_len = h->plan_len;
     // (params only for the validity checks of the raw tau / delay entries)
     return ops.episode(h->dc, st, MP_GIVEN, kernel, params, P, V, o, (hipStream_t)stream, g_err);
+  }
+  if (h->wide) {
+    // the plan GEMM first (and, when requested, the time-major info copies), then the episode over
+    // the given plans: the learned path's shape without per-env plan lengths
+    int rc = fgx_launch_traj_wide(h->dc, h->st, params, h->plan_pos, h->plan_vel, (hipStream_t)stream, g_err);
+    if (rc) return rc;
+    if (info && info->positions) {
+      rc = fgx_launch_plan_info(h->dc, h->plan_pos, h->plan_vel, info->positions, info->velocities,
+                                (hipStream_t)stream, g_err);
+      if (rc) return rc;
+    }
+    return ops.episode(h->dc, h->st, MP_GIVEN, kernel, params, h->plan_pos, h->plan_vel, o, (hipStream_t)stream, g_err);
   }
   return ops.episode(h->dc, h->st, h->dc.mp, kernel, params, nullptr, nullptr, o, (hipStream_t)stream, g_err);
 }
@@ -627,6 +692,7 @@ int fgx_trajectory(void* handle, const float* params, float* des_pos, float* des
   if (h->learned())
     return ops.traj_env(h->dc, h->st, params, h->env_tab, des_pos, des_vel, h->plan_len, nullptr, nullptr,
                         (hipStream_t)stream, g_err);
+  if (h->wide) return fgx_launch_traj_wide(h->dc, h->st, params, des_pos, des_vel, (hipStream_t)stream, g_err);
   return ops.traj(h->dc, h->st, params, des_pos, des_vel, (hipStream_t)stream, g_err);
 }
 
@@ -707,7 +773,7 @@ int fgx_episode_kernel(void* handle, int32_t info_level) {
   if (!h) return fail(FGX_E_INVALID, "null handle");
   // the function fgx_step launches by (select_kernel), asked with the info level in place of the outputs
   return select_episode_kernel(h->dc,
-                               SelectIn::from_info_level(h->dc, h->learned() ? MP_GIVEN : h->dc.mp, info_level,
+                               SelectIn::from_info_level(h->dc, h->episode_mp(), info_level,
                                                          h->learned(), h->st.rew != nullptr, device_cus()),
                                KernelOverrides::from_env());
 }

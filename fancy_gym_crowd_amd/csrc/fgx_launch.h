@@ -42,6 +42,16 @@ int fgx_launch_episode_jl(const fgx::DevCfg& c, const fgx::DevState& s, int mp, 
 int fgx_launch_episode_hp(const fgx::DevCfg& c, const fgx::DevState& s, int mp, const float* params,
                           const fgx::Outputs& o, hipStream_t stream, std::string& err);
 
+// k_traj_wide (fgx_wide.hip): the plans of a wide handle (n_basis above the episode kernels' register
+// slots, or FGX_WIDE=1) as an f32 MFMA GEMM over the shared table, every link count from one unit.
+// fgx_traj_wide_refusal: null, or why k_traj_wide cannot take the configuration (fgx_create refuses
+// it with that text).  fgx_launch_plan_info: the plans [N, T, dof] into info's [T, dof, N] arrays.
+const char* fgx_traj_wide_refusal(const fgx::DevCfg& c);
+int fgx_launch_traj_wide(const fgx::DevCfg& c, const fgx::DevState& s, const float* params, float* dpos, float* dvel,
+                         hipStream_t stream, std::string& err);
+int fgx_launch_plan_info(const fgx::DevCfg& c, const float* dpos, const float* dvel, float* info_pos, float* info_vel,
+                         hipStream_t stream, std::string& err);
+
 namespace fgx {
 // What a handle launches, per link count (include/fgx.h: n_links 1..8; base_reacher.py:17-39 takes any
 // count and bb_env_constructor forwards env kwargs, envs/registry.py:280-281): one translation unit

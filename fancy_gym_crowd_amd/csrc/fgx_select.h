@@ -30,15 +30,19 @@ enum : int {
 //                                                    k_episode_hp out; an empty value counts as unset
 //   FGX_V2=0   keeps the logging k_episode where k_episode_v2 / _v2h (and k_episode_hp's INFO form) would run
 //   FGX_HP=0   never k_episode_hp;  FGX_HP=1 also gives it the verbose-2 rows
+//   FGX_WIDE=1 a handle created under it plans with k_traj_wide wherever that kernel applies (fgx_api.hip
+//              wide_eligible), also at n_basis <= 12: the A/B and equivalence switch of the wide path
 struct KernelOverrides {
   enum Kernel { K_UNSET, K_CLASSIC, K_JP, K_WS, K_JL, K_W2, K_PAIR, K_HP, K_UNKNOWN };
   enum Switch { S_UNSET, S_OFF, S_FORCE };
   Kernel kernel = K_UNSET;
   Switch v2 = S_UNSET;   // S_OFF only
   Switch hp = S_UNSET;
+  bool wide = false;     // FGX_WIDE=1: read by fgx_create, not by select_episode_kernel
 
   static KernelOverrides from_env() {
     KernelOverrides ov;
+    if (const char* v = std::getenv("FGX_WIDE")) ov.wide = std::strcmp(v, "1") == 0;
     if (const char* v = std::getenv("FGX_EPISODE_KERNEL")) {
       static const char* const names[] = {"classic", "jp", "ws", "jl", "w2", "pair", "hp"};
       if (*v) ov.kernel = K_UNKNOWN;

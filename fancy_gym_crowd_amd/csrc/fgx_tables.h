@@ -1,6 +1,6 @@
 // fgx_tables.h — basis-table device functions (the kernels that run them once per handle are in
 // fgx_tables_k.h; k_traj_env builds per-env rows with the same functions, fgx_learned.h):
-//   rbf_row          ProMP / DMP rows: normalized-RBF basis on the phase of t_i = i*dt
+//   rbf_row[_at]     ProMP / DMP rows: normalized-RBF basis on the phase of t_i = i*dt
 //   prodmp_*         ProDMP precompute: cumulative-trapezoid integrals + homogeneous solutions
 // All values are computed in f64 and rounded once to f32 (oracle/mp.py:build_tables); every exp is
 // fgx_exp (fgx_exp.h), which oracle/mp.py:exp64 restates operation for operation, so the tables
@@ -8,6 +8,7 @@
 #pragma once
 #include "fgx_device.h"
 #include "fgx_exp.h"
+#include "fgx_npsum.h"
 
 namespace fgx {
 
@@ -19,72 +20,77 @@ __device__ inline double phase64(const DevCfg& c, double t, double tau, double d
   return fgx_exp((-alpha_x) * lin);
 }
 
-// normalized RBF at phase x, f64, all n = nb + zs + zg columns (oracle/mp.py:rbf64); centres at the
-// unbounded phase of linspace(delay - o d, delay + tau + o d, n), d = tau / (n - 2o - 1), i.e. linear
-// phase u_j = (j - o) / (n - 2o - 1) (o = num_basis_outside; 0: j / (n - 1))
-__device__ inline void rbf64(const DevCfg& c, double alpha_x, double bw, double x, double* phi) {
+// The unnormalised RBF values e_j at phase x, f64, for all n = nb + zs + zg columns, and their np.sum
+// (oracle/mp.py:rbf64: phi_j = e_j / sum); centres at the unbounded phase of
+// linspace(delay - o d, delay + tau + o d, n), d = tau / (n - 2o - 1), i.e. linear phase
+// u_j = (j - o) / (n - 2o - 1) (o = num_basis_outside; 0: j / (n - 1)).  e_j goes to e[j * es]: the
+// caller's storage (the table kernels: global scratch interleaved over the threads, any n; the per-env
+// builders: a local array, n <= kMaxBasis + 4).  DEEP: n may exceed 128 (np_sum_pairwise's stack walk).
+template <bool DEEP>
+__device__ inline double rbf_exps(const DevCfg& c, double alpha_x, double bw, double x, double* e, int es) {
   const int n = c.nb + c.zs + c.zg;
-  double cen[kMaxBasis + 4], e[kMaxBasis + 4];
-  for (int j = 0; j < n; ++j) {
+  auto centre = [&](int j) {
     const double u = (n > 1) ? (double)(j - c.nbo) / (double)(n - 2 * c.nbo - 1) : 0.0;
-    cen[j] = (c.phase == 0) ? u : fgx_exp((-alpha_x) * u);
-  }
-  for (int j = 0; j < n; ++j) {
-    double d = (n > 1) ? ((j < n - 1) ? cen[j + 1] - cen[j] : cen[n - 1] - cen[n - 2]) : 1.0;
+    return (c.phase == 0) ? u : fgx_exp((-alpha_x) * u);
+  };
+  double cj = centre(0), d = 1.0;
+  for (int j = 0; j < n; ++j) {   // d = c_{j+1} - c_j, the last one repeated
+    double cn = cj;
+    if (j < n - 1) {
+      cn = centre(j + 1);
+      d = cn - cj;
+    }
     const double h = bw / (d * d);
-    const double dd = x - cen[j];
-    e[j] = fgx_exp((-h) * (dd * dd) / 2);
+    const double dd = x - cj;
+    e[(size_t)j * es] = fgx_exp((-h) * (dd * dd) / 2);
+    cj = cn;
   }
-  double s;
-  if (n < 8) {
-    s = e[0] + 0.0;
-    for (int j = 1; j < n; ++j) s = s + e[j];
-  } else {   // numpy pairwise (8 accumulators, n <= 128)
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = e[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] = r[j] + e[i + j];
-    s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) s = s + e[i];
-  }
-  for (int j = 0; j < n; ++j) phi[j] = e[j] / s;
+  auto get = [&](int j) { return e[(size_t)j * es]; };
+  if constexpr (DEEP) return np_sum_pairwise(get, n);
+  else return np_sum_block(get, 0, n);
 }
 
-// One ProMP / DMP table row i (t_i = i*dt) for the phase (tau, delay).
-__device__ inline void rbf_row(const DevCfg& c, int i, double tau, double delay, double alpha_x, double bw,
-                               float* row) {
-  double phi[kMaxBasis + 4];
+// One ProMP / DMP table row i (t_i = i*dt) for the phase (tau, delay); e, es: rbf_exps' storage.
+template <bool DEEP>
+__device__ inline void rbf_row_at(const DevCfg& c, int i, double tau, double delay, double alpha_x, double bw,
+                                  float* row, double* e, int es) {
   const double t = (double)i * c.dt;
   const double x = phase64(c, t, tau, delay, alpha_x);
-  rbf64(c, alpha_x, bw, x, phi);
+  const double sum = rbf_exps<DEEP>(c, alpha_x, bw, x, e, es);
   if (c.mp == MP_PROMP) {
-    for (int j = 0; j < c.nb; ++j) row[j] = (float)(c.weights_scale * phi[c.zs + j]);
+    for (int j = 0; j < c.nb; ++j) row[j] = (float)(c.weights_scale * (e[(size_t)(c.zs + j) * es] / sum));
     const float t0 = (float)t, t1 = (float)((double)(i + 1) * c.dt);
     const float dt32 = t1 - t0;
     row[c.nb] = dt32;
     row[c.nb + 1] = 1.0f / dt32;     // RN(1/dt32) for div_rcp
   } else {   // DMP: psi = x * phi ; sdt = f32(s_{i+1}) - f32(s_i)
-    for (int j = 0; j < c.nb; ++j) row[j] = (float)(x * phi[c.zs + j]);
+    for (int j = 0; j < c.nb; ++j) row[j] = (float)(x * (e[(size_t)(c.zs + j) * es] / sum));
     double s0 = (t - delay) / tau, s1 = ((double)(i + 1) * c.dt - delay) / tau;
     s0 = s0 > 0.0 ? s0 : 0.0;
     s1 = s1 > 0.0 ? s1 : 0.0;
     row[c.nb] = (float)s1 - (float)s0;
   }
 }
+// the per-env builders' form (k_traj_env, learned phase: n <= kMaxBasis + 4)
+__device__ inline void rbf_row(const DevCfg& c, int i, double tau, double delay, double alpha_x, double bw,
+                               float* row) {
+  double e[kMaxBasis + 4];
+  rbf_row_at<false>(c, i, tau, delay, alpha_x, bw, row, e, 1);
+}
 
 // ProDMP fine-grid pieces at s = i*h (oracle/mp.py:prodmp_fine64): the variation-of-parameters
-// integrands k1*phi, k2*phi and the homogeneous solutions.
+// integrands k1*phi, k2*phi and the homogeneous solutions; e, es: rbf_exps' storage.
+template <bool DEEP>
 __device__ inline void prodmp_integrands(const DevCfg& c, double s, double alpha_x, double bw, double* d1,
-                                         double* d2) {
+                                         double* d2, double* e, int es) {
   const double x = fgx_exp((-alpha_x) * s);
-  double phi[kMaxBasis + 4];
-  rbf64(c, alpha_x, bw, x, phi);
-  const double e = fgx_exp(c.alpha * s / 2);
-  const double k1 = s * e * x, k2 = e * x;
+  const double sum = rbf_exps<DEEP>(c, alpha_x, bw, x, e, es);
+  const double ex = fgx_exp(c.alpha * s / 2);
+  const double k1 = s * ex * x, k2 = ex * x;
   for (int j = 0; j < c.nb; ++j) {
-    d1[j] = k1 * phi[c.zs + j];
-    d2[j] = k2 * phi[c.zs + j];
+    const double phi = e[(size_t)(c.zs + j) * es] / sum;
+    d1[j] = k1 * phi;
+    d2[j] = k2 * phi;
   }
 }
 
@@ -140,14 +146,15 @@ __device__ inline void prodmp_rows_seq(const DevCfg& c, double tau, double delay
   const bool ident = prodmp_identity(delay, c.dt, c.bdt);
   const int jmax = ident ? R - 1 : prodmp_delay_index(c.dt, c.bdt, R - 1, tau, delay, 1 << 20);
   double p1[kMaxBasis], p2[kMaxBasis], prev1[kMaxBasis], prev2[kMaxBasis], cur1[kMaxBasis], cur2[kMaxBasis];
-  prodmp_integrands(c, 0.0, alpha_x, bw, prev1, prev2);
+  double e[kMaxBasis + 4];   // (learned phase: n <= kMaxBasis + 4)
+  prodmp_integrands<false>(c, 0.0, alpha_x, bw, prev1, prev2, e, 1);
   for (int j = 0; j < nb; ++j) { p1[j] = 0.0; p2[j] = 0.0; }
   int f = 0;   // fine-grid row of p1 / p2
   for (int i = 0; i < R; ++i) {
     const int ji = ident ? i : prodmp_delay_index(c.dt, c.bdt, i, tau, delay, jmax);
     for (; f < ji; ++f) {
       const double s = (double)(f + 1) * h;
-      prodmp_integrands(c, s, alpha_x, bw, cur1, cur2);
+      prodmp_integrands<false>(c, s, alpha_x, bw, cur1, cur2, e, 1);
       for (int j = 0; j < nb; ++j) {
         p1[j] = p1[j] + h * (prev1[j] + cur1[j]) / 2;
         p2[j] = p2[j] + h * (prev2[j] + cur2[j]) / 2;

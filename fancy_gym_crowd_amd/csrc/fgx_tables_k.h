@@ -1,6 +1,6 @@
 // fgx_tables_k.h — the basis-table kernels, run once per handle by fgx_create (included by
 // fgx_api.hip only; the device functions they call are in fgx_tables.h).
-//   k_tables_rbf        ProMP / DMP rows, one thread per row
+//   k_tables_rbf        ProMP / DMP rows, one thread per row, any n = n_basis + zero pads
 //   k_tables_prodmp     ProDMP precompute on the fine grid, then the rows at j(i)
 //   k_tables_transpose  column-major copy for k_episode_jl's scalar loads
 #pragma once
@@ -8,24 +8,29 @@
 
 namespace fgx {
 
-__global__ void k_tables_rbf(DevCfg c, double tau, double delay, double alpha_x, double bw, float* tab) {
+// scratch doubles a table kernel launched with `threads` threads in all needs for its rows' n
+// exponentials: value j of thread t at es[j * threads + t]
+inline size_t tables_exp_scratch(int threads, int n) { return (size_t)threads * n; }
+
+__global__ void k_tables_rbf(DevCfg c, double tau, double delay, double alpha_x, double bw, double* es, float* tab) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= c.rows) return;
-  rbf_row(c, i, tau, delay, alpha_x, bw, tab + (size_t)i * c.stride);
+  rbf_row_at<true>(c, i, tau, delay, alpha_x, bw, tab + (size_t)i * c.stride, es + i, gridDim.x * blockDim.x);
 }
 
 // ProDMP precompute (oracle/mp.py:prodmp_fine64).  Single block; scratch dp: [Rf][2*nb] f64 over the
-// fine grid s_j = j * bdt / tau, Rf = prodmp_fine_rows(...) (= rows without a delay or own basis dt).
+// fine grid s_j = j * bdt / tau, Rf = prodmp_fine_rows(...) (= rows without a delay or own basis dt);
+// es: tables_exp_scratch(blockDim.x, n).
 __global__ void k_tables_prodmp(DevCfg c, double tau, double delay, double alpha_x, double bw, int Rf, double* dp,
-                                float* tab) {
+                                double* es, float* tab) {
   const int nb = c.nb, W = 2 * nb;
   const double h = c.bdt / tau;
   for (int i = threadIdx.x; i < Rf; i += blockDim.x)
-    prodmp_integrands(c, (double)i * h, alpha_x, bw, dp + (size_t)i * W, dp + (size_t)i * W + nb);
+    prodmp_integrands<true>(c, (double)i * h, alpha_x, bw, dp + (size_t)i * W, dp + (size_t)i * W + nb,
+                            es + threadIdx.x, blockDim.x);
   __syncthreads();
-  // cumulative trapezoid, one thread per column, sequential (same order as the oracle)
-  if ((int)threadIdx.x < W) {
-    const int j = threadIdx.x;
+  // cumulative trapezoid, one thread per column at a time, sequential in the row (same order as the oracle)
+  for (int j = threadIdx.x; j < W; j += blockDim.x) {
     double p = 0.0, prev = dp[j];
     dp[j] = 0.0;
     for (int i = 1; i < Rf; ++i) {

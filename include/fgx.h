@@ -117,7 +117,12 @@ typedef struct fgx_config {
   int32_t allow_wall_collision; /* HoleReacher only                                         */
   int32_t mp_kind;              /* FGX_MP_*                                                 */
   int32_t phase_kind;           /* FGX_PHASE_*                                              */
-  int32_t n_basis;              /* basis functions per dof (without zero padding)          */
+  int32_t n_basis;              /* basis functions per dof (without zero padding): 1..12 everywhere;
+                                   13 and above, with n_basis + zero_start + zero_goal <= 1024, on the
+                                   wide path: ProMP / ProDMP without a replanning schedule, learn_tau /
+                                   learn_delay / learn_sub_trajectories or condition_on_desired (the
+                                   plans come from an f32 MFMA GEMM, k_traj_wide; every env kind, link
+                                   count, controller and info level).  FGX_E_UNSUPPORTED otherwise */
   int32_t zero_start;           /* ZeroPaddingNormalizedRBF num_basis_zero_start            */
   int32_t zero_goal;            /* ZeroPaddingNormalizedRBF num_basis_zero_goal             */
   int32_t ctrl_kind;            /* FGX_CTRL_*                                               */

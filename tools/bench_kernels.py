@@ -167,6 +167,56 @@ def mfma_ab(env_id="fancy_ProMP/LongSimpleReacher-v0", N=65536, reps=20):
         res["fused_valu"].view(np.int64), res["mfma_plans"].view(np.int64))))), flush=True)
 
 
+def wide(env_id="fancy_ProMP/LongSimpleReacher-v0", N=65536, counts=(16, 64, 256, 1000), reps=5):
+    """The wide path (k_traj_wide + the episode over its plans, csrc/fgx_wide.h): us per black-box step
+    and k_traj_wide's own time (fgx_trajectory) per basis count, each beside the larger of its two
+    floors (the f32 MFMA peak of 157.3 TFLOP/s; the output write at the 4.7 TB/s k_traj_mfma reaches
+    for the same layout); then n_basis = 12 on the fused path and under FGX_WIDE=1
+    (the switch is read when the handle is created)."""
+    import ctypes
+
+    def one(nb, forced):
+        os.environ.pop("FGX_WIDE", None)
+        if forced:
+            os.environ["FGX_WIDE"] = "1"
+        env = fgx.make(env_id, num_envs=N, device=dev, info_level=0,
+                       mp_config_override={"basis_generator_kwargs": {"num_basis": nb}})
+        os.environ.pop("FGX_WIDE", None)
+        env.reset(seed=0)
+        T, n = env.T, env.dof
+        params = torch.randn((N, env.n_params), device=dev)
+        obs = torch.empty((N, env.out_dim), device=dev)
+        fobs = torch.empty_like(obs)
+        ret = torch.empty(N, dtype=torch.float64, device=dev)
+        te = torch.empty(N, dtype=torch.uint8, device=dev)
+        tr = torch.empty(N, dtype=torch.uint8, device=dev)
+        tl = torch.empty(N, dtype=torch.int32, device=dev)
+        t_step = timed(lambda: env.step_into(params, obs, ret, te, tr, tl, fobs), reps=reps)
+        pos = torch.empty((N, T, n), device=dev)
+        vel = torch.empty_like(pos)
+        lib, h = env._eng.lib, env._eng.h
+        args = [ctypes.c_void_p(x.data_ptr()) for x in (params, pos, vel)]
+        t_traj = timed(lambda: lib.fgx_trajectory(h, *args, env._eng.stream()), reps=reps)
+        is_wide = forced or nb > 12
+        macs = N * n * T * nb
+        mfma_floor = 2 * macs / 157.3e12
+        write_floor = 2 * N * T * n * 4 / 4.7e12
+        floor = max(mfma_floor, write_floor)
+        print(json.dumps(dict(kernel="k_traj_wide" if is_wide else "fused", config=env_id, envs=N, n_basis=nb,
+                              fgx_wide=int(forced), episode_kernel=env.episode_kernel(),
+                              us_per_bb_step=t_step * 1e6, traj_us=t_traj * 1e6, mfma_floor_us=mfma_floor * 1e6,
+                              write_floor_us=write_floor * 1e6, floor="mfma" if mfma_floor > write_floor else "write",
+                              traj_frac_of_floor=floor / t_traj, mfma_TFLOPs=2 * macs / t_traj / 1e12,
+                              params_GBps=N * env.n_params * 4 / t_traj / 1e9)), flush=True)
+        del env, params, pos, vel
+        torch.cuda.empty_cache()
+
+    for nb in counts:
+        one(nb, False)
+    one(12, False)
+    one(12, True)
+
+
 def step_raw(env_id, N, final_obs=True):
     """k_step_raw through fgx_step_raw as StepVectorEnv.step calls it (with final_obs)."""
     env = fgx.make(env_id, num_envs=N, device=dev, info_level=0)
@@ -389,5 +439,7 @@ if __name__ == "__main__":
     if "mfmaab" in which:
         mfma_ab()
         mfma_ab("fancy_ProDMP/LongSimpleReacher-v0")
+    if "wide" in which:   # n_basis 16 .. 1000 on the wide path, 12 fused and forced wide
+        wide()
     if "raw1" in which:   # config 1 alone (PMC passes)
         step_raw("fancy/SimpleReacher-v0", 1 << 20)
