@@ -44,7 +44,7 @@ def __getattr__(name):
     if name == "SingleEnv":
         from .gym_compat import SingleEnv
         return SingleEnv
-    if name in ("BlackBoxVectorEnv", "StepVectorEnv", "Box", "ResetNeeded"):
+    if name in ("BlackBoxVectorEnv", "StepVectorEnv", "Box", "ResetNeeded", "Rollout"):
         from . import vector_env
         return getattr(vector_env, name)
     raise AttributeError(name)

@@ -78,6 +78,8 @@ EXPORTS = {
                                                               ctypes.c_void_p]),
     "fgx_trajectory": (ctypes.c_int, [ctypes.c_void_p] * 5),
     "fgx_step_raw": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int32, ctypes.c_void_p]),
+    "fgx_rollout_raw": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 6 +
+                        [ctypes.c_int32, ctypes.c_void_p]),
     "fgx_get_state": (ctypes.c_int, [ctypes.c_void_p] * 7),
     "fgx_set_state": (ctypes.c_int, [ctypes.c_void_p] * 7),
     # ---- ABI 9: complete snapshots

@@ -706,6 +706,20 @@ int fgx_step_raw(void* handle, const float* actions, float* obs, double* reward,
                                    (hipStream_t)stream, g_err);
 }
 
+int fgx_rollout_raw(void* handle, const float* actions, int32_t horizon, int32_t n_cand, double* returns,
+                    int32_t* lengths, uint8_t* terminated, uint8_t* truncated, float* obs, double* rewards,
+                    int32_t commit, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(FGX_E_INVALID, "null handle");
+  if (!actions || !returns || !lengths || !terminated || !truncated) return fail(FGX_E_INVALID, "null argument");
+  if (horizon < 1) return fail(FGX_E_INVALID, "horizon must be >= 1");
+  if (n_cand < 1) return fail(FGX_E_INVALID, "n_cand must be >= 1");
+  if (commit && n_cand != 1) return fail(FGX_E_INVALID, "commit needs n_cand == 1");
+  if (h->dc.time_aware) return fail(FGX_E_UNSUPPORTED, "step-based envs have no TimeAwareObservation");
+  return nl_ops(h->dc.nl).rollout_raw(h->dc, h->st, actions, horizon, n_cand, returns, lengths, terminated, truncated,
+                                      obs, rewards, commit, (hipStream_t)stream, g_err);
+}
+
 int fgx_get_state(void* handle, double* q, double* qd, double* goal, double* hole, int32_t* steps, void* stream) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(FGX_E_INVALID, "null handle");

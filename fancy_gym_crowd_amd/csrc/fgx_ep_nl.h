@@ -2,7 +2,7 @@
 // count (include/fgx.h n_links 1..8; the reference env takes any n_links, base_reacher.py:17-39, and
 // bb_env_constructor forwards env kwargs, envs/registry.py:280-281).  Included once by each
 // fgx_ep_nl<n>.hip, which defines FGX_NL, so that the counts compile in parallel.  Reset, step-based
-// step, trajectories and the learned-phase plans are the same templates at every count.  The
+// step and rollout, trajectories and the learned-phase plans are the same templates at every count.  The
 // registered counts 2 and 5 differ in three places, all below (kRegistered<NL>):
 //   * NB: they also hold the NB = 5 forms of k_traj_valu / k_traj_env (kNB5<NL>; the others: the
 //     generic basis count NB = 0 only, any n_basis <= 12);
@@ -14,6 +14,7 @@
 #pragma once
 #include "fgx_dispatch.h"
 #include "fgx_learned.h"
+#include "fgx_rollout.h"
 #include "fgx_step.h"
 #include "fgx_traj_run.h"
 
@@ -77,6 +78,23 @@ int nl_step_raw(const DevCfg& c, const DevState& s, const float* act, float* obs
   });
 }
 
+template <int NL>
+int nl_rollout_raw(const DevCfg& c, const DevState& s, const float* act, int horizon, int n_cand, double* ret,
+                   int32_t* len, uint8_t* term, uint8_t* trunc, float* obs, double* rew, int commit, hipStream_t stream,
+                   std::string& err) {
+  const int64_t blocks = (int64_t)n_cand * ((c.N + kRolloutBlock - 1) / kRolloutBlock);
+  if (blocks > 0x7fffffff) {
+    err = "k_rollout_raw: n_cand * ceil(n_envs / 256) workgroups exceed the grid limit";
+    return -4;
+  }
+  // LDS regions of the four waves' action chunks / observation rows (k_rollout_raw, fgx_rollout_lds.h)
+  const size_t lds = (size_t)rollout_lds_bytes(NL, obs ? c.obs_dim : 0);
+  return pick<ENV_SIMPLE, ENV_HOLE, ENV_VIA>(c.env, -1, "bad env kind", err, [&](auto ENV) {
+    return launch("k_rollout_raw", k_rollout_raw<ENV, NL>, dim3((unsigned)blocks), dim3(kRolloutBlock), lds, stream, err,
+                  c, s, act, horizon, n_cand, ret, len, term, trunc, obs, rew, commit);
+  });
+}
+
 // f(MP, NB): the tags of the handle's MP kind and of the compiled basis count that serves c.nb
 // (kNB5<NL>, else the generic 0); no MP: -1 with `miss`
 template <int NL, class F>
@@ -113,6 +131,6 @@ int nl_traj_env(const DevCfg& c, const DevState& s, const float* params, float* 
 
 const fgx::NlOps* FGX_NL_CAT(fgx_nl_ops_, FGX_NL)() {
   static const fgx::NlOps ops = {nl_episode<FGX_NL>, nl_reset<FGX_NL>, nl_step_raw<FGX_NL>, nl_traj<FGX_NL>,
-                                 nl_traj_env<FGX_NL>};
+                                 nl_traj_env<FGX_NL>, nl_rollout_raw<FGX_NL>};
   return &ops;
 }

@@ -67,6 +67,10 @@ struct NlOps {
               std::string& err);
   int (*traj_env)(const DevCfg& c, const DevState& s, const float* params, float* env_tab, float* dpos, float* dvel,
                   int32_t* plan_len, float* info_pos, float* info_vel, hipStream_t stream, std::string& err);
+  // k_rollout_raw: horizon steps of n_cand action sequences per env (fgx_rollout_raw, include/fgx.h)
+  int (*rollout_raw)(const DevCfg& c, const DevState& s, const float* act, int horizon, int n_cand, double* ret,
+                     int32_t* len, uint8_t* term, uint8_t* trunc, float* obs, double* rew, int commit,
+                     hipStream_t stream, std::string& err);
 };
 }  // namespace fgx
 const fgx::NlOps* fgx_nl_ops_1();

@@ -20,6 +20,7 @@ Per-step arrays are [N, T, ...], NaN (0 for flags) after each env's trajectory_l
 
 All compute runs in libfgx.so (HIP) on the tensors' device; there is no CPU fallback.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -48,6 +49,9 @@ class Box:
 
     def __repr__(self):
         return f"Box({self.shape}, {self.dtype})"
+
+
+Rollout = collections.namedtuple("Rollout", "returns lengths terminated truncated observations rewards")
 
 
 def _ptr(t):
@@ -476,6 +480,43 @@ class StepVectorEnv:
             info["final_info"] = FinalInfo(done, {})
             info["_final_info"] = done
         return obs, rew, term, trunc, info
+
+    def rollout(self, actions, *, commit=False, observations=True, rewards=False):
+        """What would happen from here: C open-loop action sequences of H steps from every env's
+        current state in one launch (fgx_rollout_raw), without touching the envs unless `commit`.
+        actions: [H, C, N, dof], or [H, N, dof] for one candidate (the outputs then have no C
+        axis); time-major, applied unclipped as step() applies them.  Each (env, candidate) pair
+        steps as step() with autoreset off would and stops after its first terminated | truncated
+        step: L steps.  Returns Rollout(returns [C, N] f64 (r_0 + r_1 + ... in that order), lengths
+        [C, N] i32 (L), terminated, truncated [C, N] bool (of step L - 1), observations
+        [C, N, obs_dim] f32 (after step L - 1; None unless `observations`), rewards [H, C, N] f64
+        (+0.0 from step L on; None unless `rewards`)).  commit=True (one candidate only) leaves
+        every env where its L steps took it; finished envs are not auto-reset: reset them with
+        reset(options={'reset_mask': terminated | truncated}).  No random number is drawn."""
+        _order_check(self)
+        a = torch.as_tensor(actions, device=self.device).to(torch.float32).contiguous()
+        N = self.num_envs
+        if a.dim() not in (3, 4) or tuple(a.shape[-2:]) != (N, self.dof):
+            raise ValueError(f"actions must have shape [H, C, {N}, {self.dof}] or [H, {N}, {self.dof}], "
+                             f"not {list(a.shape)}")
+        H, C = int(a.shape[0]), int(a.shape[1]) if a.dim() == 4 else 1
+        if H < 1:
+            raise ValueError("actions: the horizon H (first axis) must be >= 1")
+        if C < 1:
+            raise ValueError("actions: the candidate count C (second axis) must be >= 1")
+        if commit and C != 1:
+            raise ValueError(f"commit=True needs one candidate per env, actions has C = {C}")
+        batch = (C, N) if a.dim() == 4 else (N,)
+        ret = torch.empty(batch, dtype=torch.float64, device=self.device)
+        length = torch.empty(batch, dtype=torch.int32, device=self.device)
+        te = torch.empty(batch, dtype=torch.bool, device=self.device)
+        tr = torch.empty(batch, dtype=torch.bool, device=self.device)
+        obs = torch.empty(batch + (self.obs_dim,), dtype=torch.float32, device=self.device) if observations else None
+        rew = torch.empty((H,) + batch, dtype=torch.float64, device=self.device) if rewards else None
+        _lib.check(self._eng.lib.fgx_rollout_raw(self._eng.h, _ptr(a), H, C, _ptr(ret), _ptr(length), _ptr(te),
+                                                 _ptr(tr), _ptr(obs), _ptr(rew), int(bool(commit)),
+                                                 self._eng.stream()))
+        return Rollout(ret, length, te, tr, obs, rew)
 
     def get_state(self):
         return BlackBoxVectorEnv.get_state(self)

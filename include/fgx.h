@@ -20,6 +20,8 @@
  *                     -> MPInterface.get_traj_pos/get_traj_vel          (mp_pytorch, EXTERNAL)
  *   fgx_step_raw      step-based env.step(action) (+ autoreset)         base_reacher/base_reacher_torque.py:20-37,
  *                                                                       base_reacher/base_reacher_direct.py:20-38
+ *   fgx_rollout_raw   the same env.step called H times for C action         base_reacher/base_reacher.py:98-119
+ *                     sequences per env, from its current state
  *   fgx_get_state /   env.unwrapped.current_pos/current_vel, goal, hole black_box/raw_interface_wrapper.py:24-44
  *   fgx_set_state     (test access; five of the eleven state arrays)
  *   fgx_snapshot /    the complete state of every env: bit-exact resume        (no counterpart: deepcopy /
@@ -258,6 +260,30 @@ int fgx_trajectory(void* handle, const float* params, float* des_pos, float* des
 int fgx_step_raw(void* handle, const float* actions, float* obs, double* reward,
                  uint8_t* terminated, uint8_t* truncated, float* final_obs, int32_t autoreset,
                  void* stream);
+
+/* Step-based rollouts: n_cand open-loop action sequences of `horizon` steps from every env's
+ * current state, in one launch (k_rollout_raw: the env stays in registers across the steps).  It
+ * replaces the reference's env.step loop, base_reacher.py:98-119 called `horizon` times per
+ * sequence (action repeat, frame skip, random shooting / MPPI / CEM over action sequences).
+ * For env e and candidate c, step h = 0, 1, ... applies actions[h, c, e, :] exactly as
+ * fgx_step_raw(autoreset = 0) would (same reward r_h, terminated te_h, truncated tr_h), and the
+ * sequence stops after the first h with te_h | tr_h or after h = horizon - 1; L in [1, horizon]
+ * steps are executed.  No auto-reset happens and no random number is drawn.
+ *   actions    f32 [horizon, n_cand, N, dof]   time-major, env index innermost of the batch axes
+ *   returns    f64 [n_cand, N]        ((r_0 + r_1) + r_2) + ...: left-to-right f64 adds from r_0
+ *   lengths    i32 [n_cand, N]        L
+ *   terminated, truncated  u8 [n_cand, N]   the flags of step L - 1
+ *   obs        f32 [n_cand, N, obs_dim]     the observation after step L - 1 (NULL ok)
+ *   rewards    f64 [horizon, n_cand, N]     r_h for h < L, +0.0 for h >= L (NULL ok)
+ * commit == 0: no array of the handle changes.  commit != 0 (n_cand == 1 only): every state array
+ * is what L sequential fgx_step_raw(autoreset = 0) calls would have left; the caller resets the
+ * finished envs (fgx_reset with a mask).  The same handles as fgx_step_raw.  FGX_E_INVALID: null
+ * handle or required pointer, horizon < 1, n_cand < 1, commit with n_cand != 1; FGX_E_UNSUPPORTED:
+ * time-aware handles.  One launch, stream-ordered, no host synchronisation or allocation (it can
+ * be captured in a HIP graph). */
+int fgx_rollout_raw(void* handle, const float* actions, int32_t horizon, int32_t n_cand,
+                    double* returns, int32_t* lengths, uint8_t* terminated, uint8_t* truncated,
+                    float* obs, double* rewards, int32_t commit, void* stream);
 
 /* State access (tests / checkpoint): q, qd [N, dof] f64, goal [N, 2] f64, hole [N, 3] f64
  * (HoleReacher: x, width, depth; ViaPointReacher: via x, via y, 0), steps [N] i32.

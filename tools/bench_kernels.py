@@ -244,6 +244,98 @@ def step_raw(env_id, N, final_obs=True):
                           build=fgx._lib.load().fgx_build_id().decode())), flush=True)
 
 
+def rollout(env_id, H=50, rounds=4, scale=1.0):
+    """H env-steps of 2^20 (env, candidate) pairs, three ways, alternated `rounds` times in one
+    session: (a) what the step path offers, H fgx_step_raw(autoreset = 0, final_obs = NULL) launches
+    on a 2^20-env handle captured in one HIP graph; (b) one fgx_rollout_raw launch, as N = 2^20, C = 1
+    and as N = 65536, C = 16, each with and without the per-step rewards.  Every timing starts from
+    the same restored state; the actions are small (`scale`), so no pair ends inside the horizon
+    (mean_len says so) and every form executes the same 2^20 * H env-steps.  Algorithmic bytes per
+    env-step: k_step_raw's whole-env round trip, against 4 dof (+ 8 with rewards) plus the state
+    read and the outputs once per rollout."""
+    import ctypes
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    P = 1 << 20
+    forms = {}
+    torch.manual_seed(7)
+    for N, C in ((P, 1), (P // 16, 16)):
+        env = fgx.make(env_id, num_envs=N, device=dev, autoreset=False)
+        env.reset(seed=0)
+        n, od = env.dof, env.obs_dim
+        lib, h = env._eng.lib, env._eng.h
+        act = torch.randn((H, C, N, n), device=dev) * scale
+        ret = torch.empty((C, N), dtype=torch.float64, device=dev)
+        ln = torch.empty((C, N), dtype=torch.int32, device=dev)
+        te = torch.empty((C, N), dtype=torch.uint8, device=dev)
+        tr = torch.empty((C, N), dtype=torch.uint8, device=dev)
+        obs = torch.empty((C, N, od), device=dev)
+        rews = torch.empty((H, C, N), dtype=torch.float64, device=dev)
+        sd = env.state_dict()
+        hole = 0 if "Simple" in env_id else 24
+        state = 2 * n * 8 + 16 + 8 + hole
+        keep = (env, act, ret, ln, te, tr, obs, rews, sd)
+
+        def run_rollout(with_rew, env=env, lib=lib, h=h, act=act, ret=ret, ln=ln, te=te, tr=tr, obs=obs, rews=rews, C=C):
+            fn = lambda: lib.fgx_rollout_raw(h, p(act), H, C, p(ret), p(ln), p(te), p(tr), p(obs),   # noqa: E731
+                                             p(rews) if with_rew else None, 0, env._eng.stream())
+            assert fn() == 0, lib.fgx_last_error()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / 10 * 1e-3, float(ln.double().mean().item())
+
+        for with_rew in (False, True):
+            b = n * 4 + (8 if with_rew else 0) + (state + od * 4 + 8 + 4 + 2) / H
+            forms[f"rollout N={N} C={C}" + (" +rewards" if with_rew else "")] = (
+                lambda w=with_rew, f=run_rollout: f(w), b, keep)
+        if C == 1:   # the step path on the same handle: H launches in one graph, the state restored before each replay
+            o1 = torch.empty((N, od), device=dev)
+            r1 = torch.empty(N, dtype=torch.float64, device=dev)
+            a1 = act[:, 0]
+            step = lambda k: lib.fgx_step_raw(h, p(a1[k]), p(o1), p(r1), p(te), p(tr), None, 0, env._eng.stream())   # noqa: E731
+            assert step(0) == 0, lib.fgx_last_error()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for k in range(H):
+                    step(k)
+
+            def run_steps(env=env, g=g, sd=sd):
+                ts = []
+                for _ in range(5):
+                    env.load_state_dict(sd)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts.append(e0.elapsed_time(e1) * 1e-3)
+                env.load_state_dict(sd)
+                return sum(ts) / len(ts), float(H)
+            forms[f"{H} x fgx_step_raw in one graph N={N}"] = (run_steps, n * 4 + 2 * state + od * 4 + 8 + 2, (keep, g, o1, r1))
+    times = {k: [] for k in forms}
+    lens = {}
+    for _ in range(rounds):
+        for k, (fn, _, _) in forms.items():
+            t, lens[k] = fn()
+            times[k].append(t)
+    build = fgx._lib.load().fgx_build_id().decode()
+    for k, (_, b, _) in forms.items():
+        us = sorted(x * 1e6 for x in times[k])
+        med = (us[(len(us) - 1) // 2] + us[len(us) // 2]) / 2
+        per = lambda x: x / H   # noqa: E731  (us per call -> us per env-step of all 2^20 pairs)
+        print(json.dumps(dict(kernel="k_rollout_raw" if k.startswith("rollout") else "k_step_raw", form=k, config=env_id,
+                              pairs=P, horizon=H, mean_len=lens[k], us_median=med, us_min=us[0], us_max=us[-1],
+                              us_per_env_step_median=per(med), us_per_env_step_min=per(us[0]),
+                              us_per_env_step_max=per(us[-1]), bytes_per_env_step=round(b, 2),
+                              GBps=b * P * H / (med * 1e-6) / 1e9, build=build)), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["episode", "traj", "raw"]
     if "bw" in which:   # what plain torch kernels reach on this box (write / copy streams)
@@ -441,5 +533,9 @@ if __name__ == "__main__":
         mfma_ab("fancy_ProDMP/LongSimpleReacher-v0")
     if "wide" in which:   # n_basis 16 .. 1000 on the wide path, 12 fused and forced wide
         wide()
+    if "rollout" in which:   # H = 50 steps of 2^20 pairs: the step path in one graph against k_rollout_raw
+        for env_id in ("fancy/SimpleReacher-v0", "fancy/LongSimpleReacher-v0", "fancy/HoleReacher-v0"):
+            rollout(env_id)
+            torch.cuda.empty_cache()
     if "raw1" in which:   # config 1 alone (PMC passes)
         step_raw("fancy/SimpleReacher-v0", 1 << 20)
