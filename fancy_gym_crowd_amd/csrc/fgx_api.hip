@@ -145,7 +145,8 @@ static int build_devcfg(const fgx_config& c, int64_t N, DevCfg& d, int& ctx_dim)
   if (c.ctrl_kind < FGX_CTRL_PD || c.ctrl_kind > FGX_CTRL_POS) return fail(FGX_E_INVALID, "bad ctrl_kind");
   if (c.mp_kind != FGX_MP_NONE) {
     if (c.T <= 0) return fail(FGX_E_INVALID, "T must be positive");
-    // the in-register return sum restates numpy's pairwise summation with one recursion level
+    // the return sum restates numpy's pairwise summation for up to 256 terms: one recursion level in
+    // registers up to 248, two levels over the stored step rewards from 249 on (fgx_npsum.h)
     if (c.T > 256) return fail(FGX_E_UNSUPPORTED, "plan length T > 256 not supported");
     if (c.n_basis < 1) return fail(FGX_E_UNSUPPORTED, "n_basis must be at least 1");
     if (c.zero_start < 0 || c.zero_goal < 0) return fail(FGX_E_INVALID, "zero padding counts must be >= 0");
@@ -397,7 +398,10 @@ int fgx_create(const fgx_config* cfg, int64_t n_envs, int device, void** handle)
   // step rewards of one BB step for the exact pairwise return of terminating envs (L > 128, k_episode);
   // for the direct envs also k_episode_hp's candidate final states (2 consumers x 2 n_links rows, fgx_hp.h)
   const bool direct = cfg->env_kind != FGX_ENV_SIMPLE && cfg->mp_kind != FGX_MP_NONE;
-  const bool need_rew = direct || (h->dc.sched_state && cfg->mp_kind != FGX_MP_NONE && h->dc.T > 128);
+  // SimpleReacher: state-dependent schedules (the length is not known ahead), and segments of
+  // kTwoLevelSum or more samples, which no registered id has (the online sum is exact up to 248)
+  const bool long_seg = std::min(h->dc.T, h->dc.max_steps) >= kTwoLevelSum;
+  const bool need_rew = direct || ((h->dc.sched_state || long_seg) && cfg->mp_kind != FGX_MP_NONE && h->dc.T > 128);
   const size_t rew_rows = direct ? (size_t)std::max(h->dc.T, 2 * (2 * nl)) : (size_t)h->dc.T;
   const size_t o_rew = off; off = align_up(off + (need_rew ? sizeof(double) * rew_rows * N : 0));
   e = hipMalloc(&h->state_block, off);

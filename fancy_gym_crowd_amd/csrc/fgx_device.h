@@ -13,6 +13,7 @@
 #include <string>
 #include <unordered_map>
 
+#include "fgx_npsum.h"
 #include "fgx_rng.h"
 #include "fgx_trig.h"
 
@@ -495,8 +496,10 @@ __device__ __forceinline__ bool ccw(double ax, double ay, double bx, double by, 
   return (cy - ay) * (bx - ax) - (by - ay) * (cx - ax) > 1e-12;   // classic_control/utils.py:1-2
 }
 
-// numpy pairwise summation (np.sum of a length-L f64 vector, L <= 256) done online: exact for
-// L <= 128, and for 128 < L <= 256 when split == (L/2) & ~7 (the caller knows L in advance).
+// numpy pairwise summation (np.sum of a length-L f64 vector) done online: exact for L <= 128, and
+// for 128 < L <= 248 when split == (L/2) & ~7 (the caller knows L in advance).  From L = 249 on the
+// second half L - split exceeds 128 and numpy splits it again, which first + u does not restate:
+// callers sum such lengths from stored rewards (kTwoLevelSum, pairwise_strided).
 struct PairwiseSum {
   double a[8], t;       // single-level state (valid for L <= 128)
   double b[8], u;       // second-half state (t >= split)
@@ -577,29 +580,15 @@ struct PairwiseSum {
   }
 };
 
-// numpy pairwise_sum (umath loops_utils.h) over a[0], a[st], ..., a[(n-1) st], n <= 256
+// A segment of kTwoLevelSum..256 samples has a second half of more than 128 terms, which numpy
+// splits again: PairwiseSum's one split does not give np.sum there, and the return is summed from
+// the stored step rewards (pairwise_strided) instead.
+constexpr int kTwoLevelSum = 249;
+
+// numpy pairwise_sum (umath loops_utils.h) over a[0], a[st], ..., a[(n-1) st], n <= 256: every
+// level of the recursion that such an n reaches (fgx_npsum.h np_sum_pairwise_256)
 __device__ inline double pairwise_strided(const double* a, int64_t st, int n) {
-  auto block = [&](int lo, int m) -> double {
-    if (m < 8) {
-      double r = 0.0;
-      for (int i = 0; i < m; ++i) r = r + a[(lo + i) * st];
-      return r;
-    }
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = a[(lo + j) * st];
-    int i = 8;
-    for (; i < m - (m % 8); i += 8)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r[j] = r[j] + a[(lo + i + j) * st];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < m; ++i) res = res + a[(lo + i) * st];
-    return res;
-  };
-  if (n <= 128) return block(0, n);
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return block(0, n2) + block(n2, n - n2);
+  return np_sum_pairwise_256([&](int i) { return a[i * st]; }, n);
 }
 
 // ------------------------------------------------------------------ RNG state load/store

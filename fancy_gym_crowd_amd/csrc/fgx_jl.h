@@ -476,6 +476,20 @@ __global__ __launch_bounds__((JlShape<NL>::MAXT)) void k_episode_jl(DevCfg c, De
           fast_range(max(1, na), nf, std::integral_constant<int, 2>{});
           ch = nf;
           if (8 * ch == L) { posl = plast; vell = vlast; }
+          if constexpr (PKT) {
+            // chunk nf was computed as a look-ahead (traj_fast) and runs on the generic loop below.
+            // When it holds the plan's last sample T - 1 (T not a multiple of 8, L == T) it needs the
+            // patch fast_iter gives the chunks it runs itself: Traj::at's k == T - 1 velocity
+            if (ch == cpch) {
+              float prev = vlast;
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const float vj = V[j];
+                if (j == ip) V[j] = prev;
+                prev = vj;
+              }
+            }
+          }
         }
       }
     }

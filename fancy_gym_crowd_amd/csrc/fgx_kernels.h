@@ -803,8 +803,8 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
   ps.init();
   // plan length and the numpy pairwise split point of the return sum.  SimpleReacher never
   // terminates, so its episode-segment length is known now (plan end, TimeLimit or the
-  // replanning sample) and the two-level online sum is exact; the direct envs can stop at any
-  // sample (collision) and keep their step rewards in s.rew for lengths above 128.
+  // replanning sample) and the two-level online sum is exact up to 248 samples; the direct envs can
+  // stop at any sample (collision) and keep their step rewards in s.rew for lengths above 128.
   const int Te = (MP == MP_GIVEN && s.plan_len) ? s.plan_len[e] : c.T;
   // the per-step info rows L..T-1: the full desired plan (black_box_wrapper.py:245-246), NaN (0 for
   // the flags) in the per-step arrays after trajectory_length; gen: the plan's generator at sample L.
@@ -863,13 +863,19 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
       invalid = !plan_valid<MP, NL>(c, tg, params ? params + e * c.n_params : nullptr, dpos, e, Te);
   }
   int split = 0;
+  // a SimpleReacher segment of kTwoLevelSum or more samples (custom ids with min(T, max_episode_steps)
+  // >= 249 only): the online sum's one split is not numpy's order there, so the lane stores its step
+  // rewards as the direct envs do, and its wave takes no fast blocks (which store none)
+  bool long_seg = false;
   if (ENV == ENV_SIMPLE && !c.sched_state) {
     int Lp = min(Te, max(1, c.max_steps - v.steps));
     if (k_replan >= 0) Lp = min(Lp, k_replan + 1);
     split = (Lp > 128) ? ((Lp / 2) & ~7) : 0;
+    long_seg = Lp >= kTwoLevelSum;
   }
   // only read back for segments longer than 128 samples (L <= T): shorter plans store nothing
-  double* rew_row = ((ENV != ENV_SIMPLE || c.sched_state) && s.rew && c.T > 128) ? s.rew + e : nullptr;
+  // (s.rew exists wherever a lane can ask for it: fgx_create's need_rew)
+  double* rew_row = ((ENV != ENV_SIMPLE || c.sched_state || long_seg) && s.rew && c.T > 128) ? s.rew + e : nullptr;
   bool term = false, trunc = false, stop = false;
   float pos[NL], vel[NL];
   // fast blocks are software-pipelined: sample k's f64 controller / dynamics and the f32
@@ -1138,6 +1144,7 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
     int lim = min(199, c.max_steps - 1) - v.steps;
     if (k_replan >= 0) lim = min(lim, k_replan);
     if (c.sched_state) lim = 0;   // state-dependent replanning: every sample checks the schedule
+    if (long_seg) lim = 0;        // the return is summed from stored rewards: generic samples only (wave_min below)
     // fast samples k < lim2 (sample Te - 1 ends the plan; the look-ahead of the last fast sample
     // must not be it either)
     const int lim2 = min(Te - (MP == MP_GIVEN ? 1 : 2), max(0, lim));

@@ -38,9 +38,10 @@ def _norm2(v):
 
 
 class BatchedReacher:
-    def __init__(self, name, N, random_start=None, **overrides):
+    def __init__(self, name, N, random_start=None, max_episode_steps=MAX_EPISODE_STEPS, **overrides):
         self.N = N
-        self.envs = [Reacher(name, random_start, **overrides) for _ in range(N)]   # RNG + reset sampling
+        self.max_episode_steps = max_episode_steps   # TimeLimit
+        self.envs = [Reacher(name, random_start, max_episode_steps, **overrides) for _ in range(N)]   # RNG + reset sampling
         e0 = self.envs[0]
         self.kind, self.n, self.dt = e0.kind, e0.n, e0.dt
         self.obs_dim = e0.obs_dim
@@ -273,7 +274,7 @@ class BatchedReacher:
             info["end_effector"] = self.ee.copy()
             term = coll
         self.steps = np.where(act, steps + 1, steps)
-        trunc = self.steps >= MAX_EPISODE_STEPS
+        trunc = self.steps >= self.max_episode_steps
         return self.obs(), reward, term & act, trunc & act, info
 
 
@@ -287,8 +288,9 @@ class BatchedBB:
     def __init__(self, name, N, ctrl, mp_spec=None, traj_fn=None, replan_period=0,
                  max_planning_times=np.inf, condition_on_desired=False, info_level=0,
                  time_aware=None, tables=None, env_kwargs=None, learned=None, schedule=None,
-                 reward_aggregation=np.sum):
-        self.env = BatchedReacher(name, N, **(env_kwargs or {}))
+                 reward_aggregation=np.sum, max_episode_steps=MAX_EPISODE_STEPS):
+        self.env = BatchedReacher(name, N, max_episode_steps=max_episode_steps, **(env_kwargs or {}))
+        self.max_episode_steps = max_episode_steps   # TimeLimit, time-aware divisor and table rows
         self.reward_aggregation = reward_aggregation   # black_box_wrapper.py:252
         self.N = N
         self.ctrl = ctrl
@@ -312,7 +314,7 @@ class BatchedBB:
         if traj_fn is None:
             self.T = mp_spec.T
             self.tables = tables if tables is not None else mpm.build_tables(
-                mp_spec, (MAX_EPISODE_STEPS if do_replan else 0) + self.T + 2)
+                mp_spec, (max_episode_steps if do_replan else 0) + self.T + 2)
             traj_fn = lambda params, s0, q, qd: mpm.trajectory(mp_spec, self.tables, params, s0, q, qd)
         self.traj_fn = traj_fn
         self.traj_steps = np.zeros(N, np.int64)
@@ -323,7 +325,7 @@ class BatchedBB:
 
     def _full(self, o, t_aware):
         if self.time_aware:
-            o = np.concatenate([o.astype(np.float64), (t_aware / MAX_EPISODE_STEPS)[:, None]], axis=1)
+            o = np.concatenate([o.astype(np.float64), (t_aware / self.max_episode_steps)[:, None]], axis=1)
         return o
 
     def observation(self, o):

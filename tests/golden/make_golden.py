@@ -28,8 +28,9 @@ Outputs (small .npz files):
     variants.npz  ViaPointReacher + HoleReacher rew_fct vel_acc / unbounded ("variants")
     options.npz   reset(options={'random_start'}), SimpleReacher(target=...), reward_aggregation
                   callables ("options")
+    bb_lengths.npz  TimeLimit 252 / 120 with plans of as many samples ("lengths")
 
-Run:  python tests/golden/make_golden.py [base] [variants]   (needs /root/reference; not on the GPU box)
+Run:  python tests/golden/make_golden.py [base] [variants] [options] [lengths]   (needs /root/reference; not on the GPU box)
 """
 import os
 import sys
@@ -202,14 +203,15 @@ from fancy_gym.utils.wrappers import TimeAwareObservation  # noqa: E402
 
 
 class _Spec:
-    max_episode_steps = 200
+    def __init__(self, max_episode_steps=200):
+        self.max_episode_steps = max_episode_steps
 
 
 TARGET = (1.25, -0.5)   # fixed SimpleReacher target of the "options" fixtures
 
 
 # registered kwargs: envs/__init__.py:57-65 (SimpleReacher), :658-666 (Long), :682-698 (Hole)
-def make_raw(kind):
+def make_raw(kind, M=200):
     if kind == "simple":
         env = SimpleReacherEnv(n_links=2)
     elif kind == "long":
@@ -225,8 +227,8 @@ def make_raw(kind):
         env = SimpleReacherEnv(n_links=2 if kind == "target" else 5, target=TARGET)
     else:
         raise ValueError(kind)
-    env.spec = _Spec()
-    return TimeLimit(env, 200)
+    env.spec = _Spec(M)
+    return TimeLimit(env, M)
 
 
 class StubTrajGen:
@@ -353,8 +355,10 @@ def gen_step_based():
 
 
 # ----------------------------------------------------------------------------- (iii)/(iv) BB
-def run_bb(name, kind, controller, E, n_bb, table_fn, replan=None, ctx=True, out_dict=None, bb_kw=None):
-    """E envs, reset(seed=100+i), n_bb BB steps each with autoreset; stub MP tables per (env, bb)."""
+def run_bb(name, kind, controller, E, n_bb, table_fn, replan=None, ctx=True, out_dict=None, bb_kw=None,
+           M=200, T=200):
+    """E envs, reset(seed=100+i), n_bb BB steps each with autoreset; stub MP tables per (env, bb).
+    M: the TimeLimit (and spec.max_episode_steps), T: the plan length (duration = T * dt)."""
     rng = np.random.default_rng(4321)
     wrap = {"via": VPMPWrapper}.get(kind, HRMPWrapper if kind.startswith("hole") else SRMPWrapper)
     dof = 2 if kind == "simple" else 5
@@ -362,18 +366,18 @@ def run_bb(name, kind, controller, E, n_bb, table_fn, replan=None, ctx=True, out
                             "step_obs", "step_rew", "reset_obs", "obs0", "init_time", "init_pos",
                             "init_vel", "info_a", "info_b", "info_ee")}
     for i in range(E):
-        raw = make_raw(kind)
+        raw = make_raw(kind, M)
         env = wrap(raw)
         if replan is not None:
             env = TimeAwareObservation(env)
-        n_rows = 400 if replan is not None else 200
+        n_rows = (M if replan is not None else 0) + T
         pos_t, vel_t = table_fn(rng, n_rows, dof)
-        tg = StubTrajGen(dof * 5, pos_t, vel_t)
+        tg = StubTrajGen(dof * 5, pos_t, vel_t, T=T)
         kw = dict(bb_kw or {})
         if replan is not None:
             kw["replanning_schedule"] = replan
         bb = BlackBoxWrapper(env, trajectory_generator=tg, tracking_controller=controller,
-                             duration=2.0, **kw)
+                             duration=T * 0.01, **kw)
         o0, _ = bb.reset(seed=100 + i)
         recs["obs0"].append(o0)
         recs["pos"].append(pos_t); recs["vel"].append(vel_t)
@@ -384,7 +388,7 @@ def run_bb(name, kind, controller, E, n_bb, table_fn, replan=None, ctx=True, out
             per["obs"].append(obs); per["ret"].append(float(ret)); per["term"].append(bool(te))
             per["trunc"].append(bool(tr)); per["tlen"].append(int(L))
             def pad(a, w, dt=np.float64):
-                return np.concatenate([np.asarray(a, dtype=dt).reshape(L, -1), np.full((200 - L, w), np.nan, dt)])
+                return np.concatenate([np.asarray(a, dtype=dt).reshape(L, -1), np.full((T - L, w), np.nan, dt)])
             per["actions"].append(pad(info["step_actions"], dof))
             per["step_obs"].append(pad(info["step_observations"], info["step_observations"].shape[-1], np.float32))
             per["step_rew"].append(pad(info["step_rewards"], 1)[:, 0])
@@ -395,7 +399,7 @@ def run_bb(name, kind, controller, E, n_bb, table_fn, replan=None, ctx=True, out
             else:
                 per["info_a"].append(pad(np.array(info["reward_dist"], dtype=float), 1)[:, 0])
                 per["info_b"].append(pad(np.array(info["reward_ctrl"], dtype=float), 1)[:, 0])
-                per["info_ee"].append(np.full((200, 2), np.nan))
+                per["info_ee"].append(np.full((T, 2), np.nan))
             c = tg.calls[-1]
             per["init_time"].append(c[0]); per["init_pos"].append(c[1]); per["init_vel"].append(c[2])
             if te or tr:
@@ -435,6 +439,28 @@ def gen_bb():
     # config 5: SimpleReacher + replanning every 25 steps (TimeAwareObservation inserted)
     run_bb("bb_replan", "simple", PDController(1.0, 0.1), 3, 10, simple_tab,
            replan=lambda pos, vel, obs, action, t: t % 25 == 0)
+
+
+# ----------------------------------------------------------------------------- (viii) lengths
+def gen_lengths():
+    """TimeLimits and plan lengths other than 200 (TimeLimit(env, M), spec.max_episode_steps = M for
+    TimeAwareObservation, a stub generator of T samples): 252-step episodes whose returns np.sum adds
+    over two levels of its pairwise split, and replanning with the time-aware column t / 120."""
+    out = {}
+
+    def simple_tab(rng, n, dof):
+        return smooth_tables(rng, n, dof, 1.0, 3.0)
+
+    def hole_pd_tab(rng, n, dof):
+        off = rng.uniform(-3.5, 3.5, dof)
+        off[0] = rng.uniform(0.0, np.pi)
+        return smooth_tables(rng, n, dof, 0.6, 1.0, offset=off)
+
+    run_bb("len_long", "long", PDController(0.6, 0.075), 8, 2, simple_tab, out_dict=out, M=252, T=252)
+    run_bb("len_hole", "hole", PDController(1.0, 0.1), 8, 2, hole_pd_tab, out_dict=out, M=252, T=252)
+    run_bb("len_replan", "simple", PDController(1.0, 0.1), 8, 6, simple_tab, out_dict=out, M=120, T=120,
+           replan=lambda pos, vel, obs, action, t: t % 25 == 0)
+    np.savez_compressed(os.path.join(OUT, "bb_lengths.npz"), **out)
 
 
 # ----------------------------------------------------------------------------- (vi) widening
@@ -549,7 +575,7 @@ def gen_options():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["base", "variants", "options"]
+    which = sys.argv[1:] or ["base", "variants", "options", "lengths"]
     if "base" in which:
         gen_resets()
         gen_step_based()
@@ -558,6 +584,8 @@ if __name__ == "__main__":
         gen_variants()
     if "options" in which:
         gen_options()
+    if "lengths" in which:
+        gen_lengths()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)))

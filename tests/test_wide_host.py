@@ -48,6 +48,49 @@ def test_row_sum_equals_numpy_for_every_width(tmp_path):
     assert (seq.view(np.int64) != want[-1].view(np.int64)).any()
 
 
+@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
+def test_return_sum_equals_numpy_up_to_256_terms(tmp_path):
+    """np_sum_pairwise_256 (the episode kernels' return over stored step rewards, fgx_device.h
+    pairwise_strided) against np.sum for every n in 1..256, on signed values as rewards are.  At
+    n = 249..255 numpy splits the second half (129..135 terms) again; a sum that keeps it in one
+    block differs on these rows, which the last assertion shows."""
+    exe = str(tmp_path / "npsum_check")
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-Wno-unused-result",
+                    os.path.join(HERE, "host", "npsum_check.hip"), "-o", exe], check=True)
+    rng = np.random.default_rng(256)
+    rows = 24
+    blocks, data, want = [], [], []
+    for n in range(1, 257):
+        a = -np.exp(rng.uniform(-12.0, 4.0, (rows, n))) * rng.uniform(0.5, 1.5, (rows, n))
+        a[:, ::5] *= -1.0
+        a = np.ascontiguousarray(a, np.float64)
+        blocks.append(np.array([n, rows], np.int64).tobytes() + a.tobytes())
+        data.append(a)
+        want.append(np.sum(a, axis=-1))
+    src, dst = str(tmp_path / "rows.bin"), str(tmp_path / "sums.bin")
+    with open(src, "wb") as f:
+        f.write(b"".join(blocks))
+    subprocess.run([exe, src, dst, "256"], check=True)
+    got = np.fromfile(dst, np.float64).reshape(256, rows)
+    want = np.stack(want)
+    bad = np.nonzero((got.view(np.int64) != want.view(np.int64)).any(axis=1))[0] + 1
+    assert bad.size == 0, f"sums differ from np.sum at n = {bad.tolist()}"
+    # one split only (first + the unsplit rest) is another sum from 249 terms on
+    for n in (249, 252, 255):
+        a = data[n - 1]
+        n2 = (n // 2) & ~7
+        rest = a[:, n2:]
+        r8 = rest[:, :(n - n2) & ~7].reshape(rows, -1, 8)
+        acc = r8[:, 0].copy()
+        for k in range(1, r8.shape[1]):
+            acc = acc + r8[:, k]
+        u = ((acc[:, 0] + acc[:, 1]) + (acc[:, 2] + acc[:, 3])) + ((acc[:, 4] + acc[:, 5]) + (acc[:, 6] + acc[:, 7]))
+        for j in range((n - n2) & ~7, n - n2):
+            u = u + rest[:, j]
+        one = np.sum(a[:, :n2], axis=-1) + u
+        assert (one.view(np.int64) != want[n - 1].view(np.int64)).any(), n
+
+
 @pytest.mark.parametrize("env_id,n_params", [("fancy_ProMP/LongSimpleReacher-v0", 5000),
                                              ("fancy_ProDMP/LongSimpleReacher-v0", 5005)])
 def test_registry_resolves_the_examples_override(env_id, n_params):
