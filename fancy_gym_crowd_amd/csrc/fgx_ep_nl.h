@@ -104,6 +104,35 @@ int pick_mp_nb(const DevCfg& c, const char* miss, std::string& err, F&& f) {
   });
 }
 
+// k_rollout_bb: one kernel family and one occupancy form, no selection.  THE RULE: the uncapped form
+// at every C * N; the two-waves form (amdgpu_waves_per_eu(2)) measured the same within the
+// alternation's spread at C * N = 65536 and 2^20 (ProMP LongSimpleReacher: 64.6 / 64.5 us and
+// 645.4 / 645.4 us, profiles/rollout_bb.jsonl) because the rollout body already fits 256 registers.
+template <int NL>
+int nl_rollout_bb(const DevCfg& c, const DevState& s, const float* params, int n_cand, const Outputs& o,
+                  hipStream_t stream, std::string& err) {
+  const int64_t blocks = (int64_t)n_cand * ((c.N + 255) / 256);
+  if (blocks > 0x7fffffff) {
+    err = "k_rollout_bb: n_cand * ceil(n_envs / 256) workgroups exceed the grid limit";
+    return -4;
+  }
+  const size_t lds = (size_t)c.rows * c.stride * sizeof(float);
+  return pick<ENV_SIMPLE, ENV_HOLE, ENV_VIA>(c.env, -1, "bad env kind", err, [&](auto ENV) {
+    return pick<CTRL_PD, CTRL_VEL, CTRL_POS>(c.ctrl, -1, "bad ctrl_kind", err, [&](auto CTRL) {
+      return pick_mp_nb<NL>(c, "fgx_rollout_bb needs a movement primitive", err, [&](auto MP, auto NB) {
+        if constexpr (NB != 0) {
+          if (c.stride != Traj<MP, 1, NB>::KS) {
+            err = "basis table stride does not match the compiled layout";
+            return -1;
+          }
+        }
+        return launch("k_rollout_bb launch", k_rollout_bb<ENV, MP, CTRL, NL, NB>, dim3((unsigned)blocks), dim3(256), lds,
+                      stream, err, c, s, params, o);
+      });
+    });
+  });
+}
+
 // k_traj_mfma (2 / 5 links), else k_traj_run, else k_traj_valu: the first that takes the plan
 template <int NL>
 int nl_traj(const DevCfg& c, const DevState& s, const float* params, float* dpos, float* dvel, hipStream_t stream,
@@ -131,6 +160,6 @@ int nl_traj_env(const DevCfg& c, const DevState& s, const float* params, float* 
 
 const fgx::NlOps* FGX_NL_CAT(fgx_nl_ops_, FGX_NL)() {
   static const fgx::NlOps ops = {nl_episode<FGX_NL>, nl_reset<FGX_NL>, nl_step_raw<FGX_NL>, nl_traj<FGX_NL>,
-                                 nl_traj_env<FGX_NL>, nl_rollout_raw<FGX_NL>};
+                                 nl_traj_env<FGX_NL>, nl_rollout_raw<FGX_NL>, nl_rollout_bb<FGX_NL>};
   return &ops;
 }

@@ -758,23 +758,38 @@ __device__ inline void invalid_transition(const DevCfg& c, const DevState& s, co
 // HELPED (k_episode_v2h): the logging body of waves 0..3 of a 512-thread workgroup whose waves 4..7
 // store the per-step rows; the table is staged by the kernel, each sample's rows go to one of two
 // staging slots per wave and one LDS-only workgroup barrier per sample hands them over.
-template <int ENV, int MP, int CTRL, int NL, int NB, bool LOG, bool PAIR = false, bool HELPED = false>
+// ROLL (k_rollout_bb): the same step for an (env, candidate) pair that leaves the handle as it is.
+// The policy is read under `if constexpr` only and changes four things: the workgroup covers 256 envs
+// of one candidate (grid = C * ceil(N / 256)) and the parameter / output row is cand * N + e; the step
+// rewards of long segments go to the caller's workspace (s.rew points there, [C][T][N]); nothing of
+// the env is stored (no store_env, plans, cond, auto-reset, inner-step count); the outputs go to the
+// candidate rows, the observation only where o.obs is given.
+template <int ENV, int MP, int CTRL, int NL, int NB, bool LOG, bool PAIR = false, bool HELPED = false,
+          bool ROLL = false>
 __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s, const float* __restrict__ params,
                                              const float* __restrict__ dpos, const float* __restrict__ dvel,
                                              const Outputs& o) {
   static_assert(!(PAIR && (LOG || ENV == ENV_SIMPLE)), "lane pairs serve the direct envs without per-step info");
   static_assert(!HELPED || (LOG && !PAIR), "the helped body is the logging one");
+  static_assert(!ROLL || (!LOG && !PAIR && !HELPED && MP != MP_GIVEN), "the rollout is the plain step on generated plans");
   extern __shared__ float lds_tab[];
   if (MP != MP_GIVEN && !HELPED) {
     const int n = c.rows * c.stride;
     for (int i = threadIdx.x; i < n; i += blockDim.x) lds_tab[i] = s.tables[i];
     __syncthreads();
   }
-  const int64_t tid = (int64_t)blockIdx.x * (HELPED ? 256 : blockDim.x) + threadIdx.x;
+  int64_t tid = (int64_t)blockIdx.x * (HELPED ? 256 : blockDim.x) + threadIdx.x;
+  int64_t cand = 0;   // ROLL: this workgroup's candidate
+  if constexpr (ROLL) {
+    const unsigned nblk = (unsigned)((c.N + 255) / 256);
+    cand = blockIdx.x / nblk;
+    tid = (int64_t)(blockIdx.x % nblk) * 256 + threadIdx.x;
+  }
   const int64_t e = PAIR ? (tid >> 1) : tid;
   const int pp = PAIR ? (int)(threadIdx.x & 1) : 0;
   if (e >= c.N) return;
   const int64_t N = c.N;
+  const int64_t prow = ROLL ? cand * N + e : e;   // row of the parameters and of the outputs
   FGX_STAMP(o, e, 6);
   FGX_STAMP(o, e, 0);
 
@@ -792,7 +807,7 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
     ic_qd[k] = has_cond ? (double)s.cond[(NL + k) * N + e] : v.qd[k];
   }
   Traj<(MP == MP_GIVEN ? MP_NONE : MP), NL, NB, false, ENV == ENV_SIMPLE> tg;
-  if (MP != MP_GIVEN) tg.init(c, params + e * c.n_params, lds_tab, s0, ic_q, ic_qd);
+  if (MP != MP_GIVEN) tg.init(c, params + prow * c.n_params, lds_tab, s0, ic_q, ic_qd);
 
   plans += 1;
   // first sample index k with (k + 1 + s0) % replan == 0 (black_box_wrapper.py:233); the loop
@@ -875,7 +890,8 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
   }
   // only read back for segments longer than 128 samples (L <= T): shorter plans store nothing
   // (s.rew exists wherever a lane can ask for it: fgx_create's need_rew)
-  double* rew_row = ((ENV != ENV_SIMPLE || c.sched_state || long_seg) && s.rew && c.T > 128) ? s.rew + e : nullptr;
+  double* rew_row = ((ENV != ENV_SIMPLE || c.sched_state || long_seg) && s.rew && c.T > 128)
+                        ? s.rew + (ROLL ? cand * c.T * N : 0) + e : nullptr;
   bool term = false, trunc = false, stop = false;
   float pos[NL], vel[NL];
   // fast blocks are software-pipelined: sample k's f64 controller / dynamics and the f32
@@ -990,7 +1006,7 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
     bool replan_now = (k == k_replan);
     if (J < 0 && c.sched_state && plans_ok && !replan_now) replan_now = state_replan(c, v);
     if (term || trunc || replan_now) {
-      if (c.cond_desired) {
+      if (!ROLL && c.cond_desired) {   // (the rollout reads the stored condition and never writes it)
 #pragma unroll
         for (int d = 0; d < NL; ++d) { s.cond[d * N + e] = pos[d]; s.cond[(NL + d) * N + e] = vel[d]; }
         v.flags |= 2u;
@@ -1281,7 +1297,16 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
       }
     }
   }
-  episode_epilogue(c, s, o, e, v, plans, L, ret, term, trunc, !PAIR);
+  if constexpr (ROLL) {
+    // episode_epilogue's outputs without auto-reset, on the candidate row; no state leaves the thread
+    o.ret[prow] = ret;
+    o.term[prow] = term;
+    o.trunc[prow] = trunc;
+    o.tlen[prow] = L;
+    if (o.obs) emit_obs(c, v, c.return_context, o.obs + prow * c.out_dim, nullptr, false, true);
+  } else {
+    episode_epilogue(c, s, o, e, v, plans, L, ret, term, trunc, !PAIR);
+  }
   FGX_STAMP(o, e, 5);
   FGX_STAMP(o, e, 7);
 }
@@ -1370,6 +1395,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     DevCfg c, DevState s, const float* __restrict__ params, const float* __restrict__ dpos,
     const float* __restrict__ dvel, Outputs o) {
   episode_body<ENV, MP, CTRL, NL, NB, LOG>(c, s, params, dpos, dvel, o);
+}
+
+// k_rollout_bb: the black-box step of C candidate parameter rows per env from the handle's current
+// state, one thread per (env, candidate), nothing of the handle written (fgx_rollout_bb, include/fgx.h;
+// the reference: black_box_wrapper.py:170-253 called on copies of the env).  The body is
+// episode_body's (ROLL): a workgroup covers 256 consecutive envs of one candidate, so the state loads
+// [rows][N] coalesce by e, the parameter rows and outputs sit at cand * N + e, and the shared basis
+// table is staged in LDS per workgroup as in k_episode.  s.rew: the caller's workspace [C][T][N].
+// One occupancy form: without the auto-reset and the state stores the 5-link SimpleReacher bodies
+// need 198 .. 226 registers (NB = 5), so two waves per SIMD are resident without a cap; the form
+// compiled with amdgpu_waves_per_eu(2) (k_episode_w2's) measured the same time and is not built.
+template <int ENV, int MP, int CTRL, int NL, int NB>
+__global__ __launch_bounds__(256) void k_rollout_bb(DevCfg c, DevState s, const float* __restrict__ params, Outputs o) {
+  episode_body<ENV, MP, CTRL, NL, NB, false, false, false, true>(c, s, params, nullptr, nullptr, o);
 }
 
 // info_level 2, SimpleReacher: the per-step observation components that need trigonometry -- cos /

@@ -71,6 +71,10 @@ struct NlOps {
   int (*rollout_raw)(const DevCfg& c, const DevState& s, const float* act, int horizon, int n_cand, double* ret,
                      int32_t* len, uint8_t* term, uint8_t* trunc, float* obs, double* rew, int commit,
                      hipStream_t stream, std::string& err);
+  // k_rollout_bb: the black-box step of n_cand parameter rows per env, the handle left as it is
+  // (fgx_rollout_bb, include/fgx.h); s.rew: the caller's workspace, o: the candidate-row outputs
+  int (*rollout_bb)(const DevCfg& c, const DevState& s, const float* params, int n_cand, const Outputs& o,
+                    hipStream_t stream, std::string& err);
 };
 }  // namespace fgx
 const fgx::NlOps* fgx_nl_ops_1();

@@ -186,6 +186,7 @@ class BlackBoxVectorEnv:
         self._te = torch.empty(N, dtype=torch.uint8, device=dev)
         self._tr = torch.empty(N, dtype=torch.uint8, device=dev)
         self._len = torch.empty(N, dtype=torch.int32, device=dev)
+        self._rollout_ws = {}   # rollout(): candidate count C -> (workspace tensor or None, bytes)
 
     # ------------------------------------------------------------------ gymnasium-style API
     def reset(self, *, seed=None, options=None):
@@ -334,6 +335,58 @@ class BlackBoxVectorEnv:
         vel = torch.empty_like(pos)
         _lib.check(self._eng.lib.fgx_trajectory(self._eng.h, _ptr(a), _ptr(pos), _ptr(vel), self._eng.stream()))
         return pos, vel
+
+    def rollout(self, params, *, observations=True):
+        """What would happen from here: the BB step of C candidate parameter vectors per env from
+        every env's current state in one launch (fgx_rollout_bb), with the envs left untouched: no
+        state, plan count, RNG stream or auto-reset.  params: [C, N, n_params], or [N, n_params]
+        for one candidate (the outputs then have no C axis).  Each (env, candidate) pair gives bit
+        for bit what step(params[c]) gives on a copy of the env with autoreset off.  Returns
+        (returns [C, N] f64, lengths [C, N] i32, terminated, truncated [C, N] bool, observations
+        [C, N, out_dim] f32 after the last sample, or None unless `observations`).
+        reward_aggregation must be sum or mean: the others read per-step rewards, which this call
+        does not return."""
+        _order_check(self)
+        agg = self.meta["reward_aggregation"]
+        if agg not in ("sum", "mean"):
+            raise ValueError("rollout() serves reward_aggregation np.sum / np.mean only: the others read the "
+                             "per-step rewards, which rollout() does not return")
+        a = torch.as_tensor(params, device=self.device)
+        N = self.num_envs
+        if a.dim() not in (2, 3) or tuple(a.shape[-2:]) != (N, self.n_params):
+            raise ValueError(f"params must have shape [C, {N}, {self.n_params}] or [{N}, {self.n_params}], "
+                             f"not {list(a.shape)}")
+        C = int(a.shape[0]) if a.dim() == 3 else 1
+        if C < 1:
+            raise ValueError("params: the candidate count C (first axis) must be >= 1")
+        a = a.to(torch.float32).contiguous()
+        ws, nbytes = self._rollout_workspace(C)
+        batch = (C, N) if a.dim() == 3 else (N,)
+        ret = torch.empty(batch, dtype=torch.float64, device=self.device)
+        length = torch.empty(batch, dtype=torch.int32, device=self.device)
+        te = torch.empty(batch, dtype=torch.bool, device=self.device)
+        tr = torch.empty(batch, dtype=torch.bool, device=self.device)
+        obs = torch.empty(batch + (self.out_dim,), dtype=torch.float32, device=self.device) if observations else None
+        _lib.check(self._eng.lib.fgx_rollout_bb(self._eng.h, _ptr(a), C, _ptr(ret), _ptr(length), _ptr(te), _ptr(tr),
+                                                _ptr(obs), _ptr(ws), nbytes, self._eng.stream()))
+        if agg == "mean":
+            ret = torch.where(length > 0, ret / length.to(torch.float64), ret)
+        return ret, length, te, tr, obs
+
+    def _rollout_workspace(self, C):
+        """The cached device workspace of rollout() for C candidates (fgx_rollout_bb_workspace: the
+        step rewards of long segments; None where none is needed).  Allocated on the first call
+        with that C, never inside a graph capture."""
+        cache = self._rollout_ws
+        if C not in cache:
+            n = ctypes.c_int64()
+            _lib.check(self._eng.lib.fgx_rollout_bb_workspace(self._eng.h, C, ctypes.byref(n)))
+            if n.value > 0 and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"the first rollout() with C = {C} allocates its workspace: "
+                                   "run it once outside the graph capture")
+            cache[C] = (torch.empty(n.value // 8, dtype=torch.float64, device=self.device) if n.value > 0 else None,
+                        n.value)
+        return cache[C]
 
     # ------------------------------------------------------------------ fast path (bench)
     def step_into(self, actions, obs, ret, te, tr, tl, fobs=None, inner_steps=None):

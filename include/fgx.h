@@ -22,6 +22,8 @@
  *                                                                       base_reacher/base_reacher_direct.py:20-38
  *   fgx_rollout_raw   the same env.step called H times for C action         base_reacher/base_reacher.py:98-119
  *                     sequences per env, from its current state
+ *   fgx_rollout_bb    BlackBoxWrapper.step(action) called on copies of the  black_box/black_box_wrapper.py:170-253
+ *                     env, once per candidate parameter vector
  *   fgx_get_state /   env.unwrapped.current_pos/current_vel, goal, hole black_box/raw_interface_wrapper.py:24-44
  *   fgx_set_state     (test access; five of the eleven state arrays)
  *   fgx_snapshot /    the complete state of every env: bit-exact resume        (no counterpart: deepcopy /
@@ -284,6 +286,37 @@ int fgx_step_raw(void* handle, const float* actions, float* obs, double* reward,
 int fgx_rollout_raw(void* handle, const float* actions, int32_t horizon, int32_t n_cand,
                     double* returns, int32_t* lengths, uint8_t* terminated, uint8_t* truncated,
                     float* obs, double* rewards, int32_t commit, void* stream);
+
+/* Black-box candidate rollouts: the black-box step of n_cand parameter vectors per env from the
+ * env's current state, in one launch (k_rollout_bb: one thread per (env, candidate)), with nothing of
+ * the handle changed.  It replaces black_box_wrapper.py:170-253 called on copies of the env
+ * (population evaluation on common contexts, parameter-space MPC at a replan point, look-ahead).
+ * For env e and candidate c every output is bit for bit what
+ *   fgx_step(handle', params[c], ..., final_obs = NULL, info = NULL, autoreset = 0)
+ * gives on a copy handle' of the handle in its current state: plan start row and initial conditions
+ * (condition_on_desired's stored values are read, never written), plans against max_planning_times,
+ * the replanning schedule, TimeLimit, controller and clip, the env step, the return in numpy's
+ * pairwise order (np.sum / np.mean aggregation), time-aware column, context mask and the
+ * observation after the last sample.
+ *   params     f32 [n_cand, N, n_params]     env index innermost of the batch axes
+ *   returns    f64 [n_cand, N]
+ *   lengths    i32 [n_cand, N]               trajectory_length
+ *   terminated, truncated  u8 [n_cand, N]
+ *   obs        f32 [n_cand, N, out_obs_dim]  (NULL ok)
+ *   workspace  fgx_rollout_bb_workspace(handle, n_cand) bytes of device memory, 8-byte aligned (NULL ok
+ *              where that is 0): the step rewards of segments longer than 128 samples, which
+ *              fgx_step keeps in the handle's own scratch (direct envs, state-dependent schedules,
+ *              SimpleReacher segments of 249 or more samples).  Contents on return are unspecified.
+ * No state array, plans, cond, RNG stream or handle-owned scratch is written; no auto-reset happens,
+ * no random number is drawn and the inner-step counter is not touched.  FGX_E_INVALID: null handle or
+ * required pointer, n_cand < 1, workspace too small; FGX_E_UNSUPPORTED: handles without a movement
+ * primitive, learned phase parameters and wide handles (their plan buffers hold N plans), handles
+ * with valid_flags != 0.  One launch, stream-ordered, no host synchronisation or allocation (it can
+ * be captured in a HIP graph). */
+int fgx_rollout_bb_workspace(void* handle, int32_t n_cand, int64_t* bytes);
+int fgx_rollout_bb(void* handle, const float* params, int32_t n_cand, double* returns,
+                   int32_t* lengths, uint8_t* terminated, uint8_t* truncated, float* obs,
+                   void* workspace, int64_t workspace_bytes, void* stream);
 
 /* State access (tests / checkpoint): q, qd [N, dof] f64, goal [N, 2] f64, hole [N, 3] f64
  * (HoleReacher: x, width, depth; ViaPointReacher: via x, via y, 0), steps [N] i32.

@@ -336,8 +336,104 @@ def rollout(env_id, H=50, rounds=4, scale=1.0):
                               GBps=b * P * H / (med * 1e-6) / 1e9, build=build)), flush=True)
 
 
+def rollout_bb(env_id, N, C, rounds=4, reps=5):
+    """The black-box step of C candidates per env at N envs, alternated `rounds` times in one session.
+    (a) the route without fgx_rollout_bb, timed as its two parts: the fgx_copy_envs fan-out of the N
+    envs into a handle of N * C envs, and one fgx_step(autoreset = 0) on that handle (its own kernel
+    choice); (b) fgx_rollout_bb.  Every form runs the same N * C episodes from the same
+    state; HIP events around `reps` eager launches.  Also: the device memory the N * C handle holds
+    (state snapshot bytes as a lower bound) beside the rollout's workspace."""
+    import ctypes
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    env = fgx.make(env_id, num_envs=N, device=dev, info_level=0, autoreset=False)
+    big = fgx.make(env_id, num_envs=N * C, device=dev, info_level=0, autoreset=False)
+    env.reset(seed=0)
+    big.reset(seed=0)
+    lib = env._eng.lib
+    params = torch.from_numpy(np.random.default_rng(1234).standard_normal((C, N, env.n_params), dtype=np.float32)).to(dev)
+    flat = params.reshape(C * N, env.n_params)
+    src = torch.arange(N, device=dev).repeat(C)
+    dst = torch.arange(N * C, device=dev)
+    M = N * C
+    ret = torch.empty((C, N), dtype=torch.float64, device=dev)
+    ln = torch.empty((C, N), dtype=torch.int32, device=dev)
+    te = torch.empty((C, N), dtype=torch.uint8, device=dev)
+    tr = torch.empty((C, N), dtype=torch.uint8, device=dev)
+    obs = torch.empty((C, N, env.out_dim), device=dev)
+    b_ret, b_ln, b_te, b_tr, b_obs = (torch.empty_like(x) for x in (ret, ln, te, tr, obs))
+    nws = ctypes.c_int64()
+    assert lib.fgx_rollout_bb_workspace(env._eng.h, C, ctypes.byref(nws)) == 0, lib.fgx_last_error()
+    ws = torch.empty(nws.value // 8, dtype=torch.float64, device=dev) if nws.value else None
+    nbig = ctypes.c_int64()
+    assert lib.fgx_snapshot_bytes(big._eng.h, ctypes.byref(nbig)) == 0
+
+    def many(fn):
+        assert fn() == 0, lib.fgx_last_error()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3   # us per call
+
+    def copy():
+        return lib.fgx_copy_envs(big._eng.h, env._eng.h, p(dst), p(src), M, env._eng.stream())
+
+    def step():   # (autoreset off and the same parameters: every call starts from the copied state again
+        # only after a copy, so each timed step is preceded by one)
+        return lib.fgx_step(big._eng.h, p(flat), p(b_obs), p(b_ret), p(b_te), p(b_tr), p(b_ln), None, None, 0,
+                            env._eng.stream())
+
+    def roll():
+        return lib.fgx_rollout_bb(env._eng.h, p(params), C, p(ret), p(ln), p(te), p(tr), p(obs), p(ws), nws.value,
+                                  env._eng.stream())
+
+    def time_step():   # one copy before every step, outside the events
+        ts = []
+        for _ in range(reps):
+            assert copy() == 0
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            assert step() == 0, lib.fgx_last_error()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        return sum(ts) / len(ts)
+
+    forms = {"a: fgx_copy_envs fan-out": lambda: many(copy), "a: fgx_step on N*C envs": time_step,
+             "b: fgx_rollout_bb": lambda: many(roll)}
+    times = {k: [] for k in forms}
+    for _ in range(rounds):
+        for k, fn in forms.items():
+            times[k].append(fn())
+    # the same episodes: the rollout's outputs are the big handle's
+    assert copy() == 0 and step() == 0 and roll() == 0
+    torch.cuda.synchronize()
+    same = bool(torch.equal(ret.reshape(-1).view(torch.int64), b_ret.reshape(-1).view(torch.int64)) and
+                torch.equal(ln.reshape(-1), b_ln.reshape(-1)))
+    build = lib.fgx_build_id().decode()
+    med = lambda v: (sorted(v)[(len(v) - 1) // 2] + sorted(v)[len(v) // 2]) / 2   # noqa: E731
+    for k, v in times.items():
+        print(json.dumps(dict(mode="rollout_bb", form=k, config=env_id, envs=N, n_cand=C, pairs=M,
+                              step_kernel=big.episode_kernel(), us_median=med(v), us_min=min(v), us_max=max(v),
+                              rounds=rounds, same_bits_as_step=same, workspace_bytes=nws.value,
+                              big_handle_snapshot_bytes=nbig.value, build=build)), flush=True)
+    a_tot = [x + y for x, y in zip(times["a: fgx_copy_envs fan-out"], times["a: fgx_step on N*C envs"])]
+    print(json.dumps(dict(mode="rollout_bb", form="a: total (copy + step)", config=env_id, envs=N, n_cand=C, pairs=M,
+                          us_median=med(a_tot), us_min=min(a_tot), us_max=max(a_tot), rounds=rounds, build=build)),
+          flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["episode", "traj", "raw"]
+    if "rollout_bb" in which:   # C = 16 candidates per env: the copy + step route against fgx_rollout_bb
+        for env_id in ("fancy_ProMP/LongSimpleReacher-v0", "fancy_ProDMP/HoleReacher-v0"):
+            for n in (65536, 4096):
+                rollout_bb(env_id, n, 16)
+                torch.cuda.empty_cache()
     if "bw" in which:   # what plain torch kernels reach on this box (write / copy streams)
         for mb in (524, 2048):
             n = mb * (1 << 20) // 4
