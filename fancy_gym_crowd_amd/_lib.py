@@ -83,6 +83,8 @@ EXPORTS = {
     "fgx_rollout_bb_workspace": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
     "fgx_rollout_bb": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] + [ctypes.c_void_p] * 6 +
                        [ctypes.c_int64, ctypes.c_void_p]),
+    "fgx_rollout_bb_seq": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 9 +
+                           [ctypes.c_int64, ctypes.c_void_p]),
     "fgx_get_state": (ctypes.c_int, [ctypes.c_void_p] * 7),
     "fgx_set_state": (ctypes.c_int, [ctypes.c_void_p] * 7),
     # ---- ABI 9: complete snapshots

@@ -724,14 +724,16 @@ int fgx_rollout_raw(void* handle, const float* actions, int32_t horizon, int32_t
                                       obs, rewards, commit, (hipStream_t)stream, g_err);
 }
 
-// null, or why k_rollout_bb does not take the handle (FGX_E_UNSUPPORTED)
+// null, or why k_rollout_bb / k_rollout_seq do not take the handle (FGX_E_UNSUPPORTED: refuse_rollout puts the
+// entry point's name in front)
 static const char* rollout_bb_refusal(const Handle* h) {
-  if (h->dc.mp == MP_NONE) return "fgx_rollout_bb: step-based handle without a movement primitive (use fgx_rollout_raw)";
-  if (h->learned()) return "fgx_rollout_bb: learned phase parameters (learn_tau / learn_delay / learn_sub_trajectories) are not served: the per-env plan buffers hold N plans";
-  if (h->wide) return "fgx_rollout_bb: wide handles are not served: the plan buffers hold N plans";
-  if (h->dc.valid_flags) return "fgx_rollout_bb: trajectory validity (valid_flags) is not served: only the logging step evaluates it";
+  if (h->dc.mp == MP_NONE) return "step-based handle without a movement primitive (use fgx_rollout_raw)";
+  if (h->learned()) return "learned phase parameters (learn_tau / learn_delay / learn_sub_trajectories) are not served: the per-env plan buffers hold N plans";
+  if (h->wide) return "wide handles are not served: the plan buffers hold N plans";
+  if (h->dc.valid_flags) return "trajectory validity (valid_flags) is not served: only the logging step evaluates it";
   return nullptr;
 }
+static int refuse_rollout(const char* fn, const char* why) { return fail(FGX_E_UNSUPPORTED, std::string(fn) + ": " + why); }
 
 // the step rewards [n_cand][T][N] where fgx_step would use the handle's [T][N] scratch (episode_body's rew_row)
 static int64_t rollout_bb_bytes(const Handle* h, int32_t n_cand) {
@@ -743,7 +745,7 @@ int fgx_rollout_bb_workspace(void* handle, int32_t n_cand, int64_t* bytes) {
   if (!h) return fail(FGX_E_INVALID, "null handle");
   if (!bytes) return fail(FGX_E_INVALID, "null argument");
   if (n_cand < 1) return fail(FGX_E_INVALID, "n_cand must be >= 1");
-  if (const char* why = rollout_bb_refusal(h)) return fail(FGX_E_UNSUPPORTED, why);
+  if (const char* why = rollout_bb_refusal(h)) return refuse_rollout("fgx_rollout_bb", why);
   *bytes = rollout_bb_bytes(h, n_cand);
   return FGX_OK;
 }
@@ -755,7 +757,7 @@ int fgx_rollout_bb(void* handle, const float* params, int32_t n_cand, double* re
   if (!h) return fail(FGX_E_INVALID, "null handle");
   if (!params || !returns || !lengths || !terminated || !truncated) return fail(FGX_E_INVALID, "null argument");
   if (n_cand < 1) return fail(FGX_E_INVALID, "n_cand must be >= 1");
-  if (const char* why = rollout_bb_refusal(h)) return fail(FGX_E_UNSUPPORTED, why);
+  if (const char* why = rollout_bb_refusal(h)) return refuse_rollout("fgx_rollout_bb", why);
   const int64_t need = rollout_bb_bytes(h, n_cand);
   if (need > 0 && (!workspace || workspace_bytes < need))
     return fail(FGX_E_INVALID, "fgx_rollout_bb: workspace too small (fgx_rollout_bb_workspace gives the size)");
@@ -768,6 +770,32 @@ int fgx_rollout_bb(void* handle, const float* params, int32_t n_cand, double* re
   DevState st = h->st;   // the handle's arrays, read only; the step rewards go to the caller's workspace
   st.rew = need > 0 ? (double*)workspace : nullptr;
   return nl_ops(h->dc.nl).rollout_bb(h->dc, st, params, n_cand, o, (hipStream_t)stream, g_err);
+}
+
+int fgx_rollout_bb_seq(void* handle, const float* params, int32_t n_seg, int32_t n_cand, double* returns,
+                       int32_t* lengths, int32_t* segments, uint8_t* terminated, uint8_t* truncated, float* obs,
+                       double* seg_returns, int32_t* seg_lengths, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(FGX_E_INVALID, "null handle");
+  if (!params || !returns || !lengths || !segments || !terminated || !truncated)
+    return fail(FGX_E_INVALID, "null argument");
+  if (n_seg < 1) return fail(FGX_E_INVALID, "n_seg must be >= 1");
+  if (n_cand < 1) return fail(FGX_E_INVALID, "n_cand must be >= 1");
+  if (const char* why = rollout_bb_refusal(h)) return refuse_rollout("fgx_rollout_bb_seq", why);
+  const int64_t need = rollout_bb_bytes(h, n_cand);
+  if (need > 0 && (!workspace || workspace_bytes < need))
+    return fail(FGX_E_INVALID, "fgx_rollout_bb_seq: workspace too small (fgx_rollout_bb_workspace gives the size)");
+  Outputs o = {};
+  o.obs = obs;
+  o.ret = returns;
+  o.term = terminated;
+  o.trunc = truncated;
+  o.tlen = lengths;
+  DevState st = h->st;   // the handle's arrays, read only; the step rewards go to the caller's workspace
+  st.rew = need > 0 ? (double*)workspace : nullptr;
+  return nl_ops(h->dc.nl).rollout_seq(h->dc, st, params, n_seg, n_cand, o, segments, seg_returns, seg_lengths,
+                                      (hipStream_t)stream, g_err);
 }
 
 int fgx_get_state(void* handle, double* q, double* qd, double* goal, double* hole, int32_t* steps, void* stream) {

@@ -14,6 +14,7 @@
 #pragma once
 #include "fgx_dispatch.h"
 #include "fgx_learned.h"
+#include "fgx_nl_pick.h"
 #include "fgx_rollout.h"
 #include "fgx_step.h"
 #include "fgx_traj_run.h"
@@ -21,13 +22,15 @@
 #define FGX_NL_CAT2(a, b) a##b
 #define FGX_NL_CAT(a, b) FGX_NL_CAT2(a, b)
 
+// k_rollout_seq of this link count: a unit of its own (fgx_seq_nl<n>.hip -> fgx_seq_nl.h)
+int FGX_NL_CAT(fgx_launch_rollout_seq_, FGX_NL)(const fgx::DevCfg& c, const fgx::DevState& s, const float* params,
+                                                int n_seg, int n_cand, const fgx::Outputs& o, int32_t* segments,
+                                                double* seg_ret, int32_t* seg_len, hipStream_t stream,
+                                                std::string& err);
+
 namespace {
 using namespace fgx;
-template <int NL>
-constexpr bool kRegistered = NL == 2 || NL == 5;
-// the compiled basis count besides the generic NB = 0 (the registered counts: 5; the others: none)
-template <int NL>
-constexpr int kNB5 = kRegistered<NL> ? 5 : 0;
+// (kRegistered<NL>, kNB5<NL> and pick_mp_nb<NL>: fgx_nl_pick.h)
 
 // (templates on the count, so that `if constexpr` leaves the branch not taken uninstantiated)
 template <int NL>
@@ -95,15 +98,6 @@ int nl_rollout_raw(const DevCfg& c, const DevState& s, const float* act, int hor
   });
 }
 
-// f(MP, NB): the tags of the handle's MP kind and of the compiled basis count that serves c.nb
-// (kNB5<NL>, else the generic 0); no MP: -1 with `miss`
-template <int NL, class F>
-int pick_mp_nb(const DevCfg& c, const char* miss, std::string& err, F&& f) {
-  return pick<MP_PROMP, MP_DMP, MP_PRODMP>(c.mp, -1, miss, err, [&](auto MP) {
-    return pick<kNB5<NL>, 0>(c.nb == kNB5<NL> ? c.nb : 0, -1, miss, err, [&](auto NB) { return f(MP, NB); });
-  });
-}
-
 // k_rollout_bb: one kernel family and one occupancy form, no selection.  THE RULE: the uncapped form
 // at every C * N; the two-waves form (amdgpu_waves_per_eu(2)) measured the same within the
 // alternation's spread at C * N = 65536 and 2^20 (ProMP LongSimpleReacher: 64.6 / 64.5 us and
@@ -160,6 +154,7 @@ int nl_traj_env(const DevCfg& c, const DevState& s, const float* params, float* 
 
 const fgx::NlOps* FGX_NL_CAT(fgx_nl_ops_, FGX_NL)() {
   static const fgx::NlOps ops = {nl_episode<FGX_NL>, nl_reset<FGX_NL>, nl_step_raw<FGX_NL>, nl_traj<FGX_NL>,
-                                 nl_traj_env<FGX_NL>, nl_rollout_raw<FGX_NL>, nl_rollout_bb<FGX_NL>};
+                                 nl_traj_env<FGX_NL>, nl_rollout_raw<FGX_NL>, nl_rollout_bb<FGX_NL>,
+                                 FGX_NL_CAT(fgx_launch_rollout_seq_, FGX_NL)};
   return &ops;
 }

@@ -764,14 +764,29 @@ __device__ inline void invalid_transition(const DevCfg& c, const DevState& s, co
 // rewards of long segments go to the caller's workspace (s.rew points there, [C][T][N]); nothing of
 // the env is stored (no store_env, plans, cond, auto-reset, inner-step count); the outputs go to the
 // candidate rows, the observation only where o.obs is given.
+// SEQ (k_rollout_seq, with ROLL): the pair runs up to seq.n_seg successive steps, segment g on the
+// parameter row params[g][cand][e], with the env, `plans` and the condition_on_desired values held in
+// registers from one segment to the next.  Everything from the plan start row to the segment's return is
+// the code below, entered again per segment (next_segment); a pair whose segment ended the episode, or
+// was the last one, writes its outputs and leaves the loop by a divergent return, so the wave-wide
+// operations of the later segments (__ballot, readfirstlane, wave_min) see the running lanes only, as
+// they do after `if (e >= c.N) return`.  No workgroup barrier follows the table staging.
+struct SeqArgs {
+  int n_seg = 1, n_cand = 1;
+  int32_t* segments = nullptr;     // [C][N] segments executed
+  double* seg_ret = nullptr;       // [S][C][N] or null
+  int32_t* seg_len = nullptr;      // [S][C][N] or null
+};
+
 template <int ENV, int MP, int CTRL, int NL, int NB, bool LOG, bool PAIR = false, bool HELPED = false,
-          bool ROLL = false>
+          bool ROLL = false, bool SEQ = false>
 __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s, const float* __restrict__ params,
                                              const float* __restrict__ dpos, const float* __restrict__ dvel,
-                                             const Outputs& o) {
+                                             const Outputs& o, const SeqArgs& seq = SeqArgs{}) {
   static_assert(!(PAIR && (LOG || ENV == ENV_SIMPLE)), "lane pairs serve the direct envs without per-step info");
   static_assert(!HELPED || (LOG && !PAIR), "the helped body is the logging one");
   static_assert(!ROLL || (!LOG && !PAIR && !HELPED && MP != MP_GIVEN), "the rollout is the plain step on generated plans");
+  static_assert(!SEQ || ROLL, "segment sequences are a rollout form");
   extern __shared__ float lds_tab[];
   if (MP != MP_GIVEN && !HELPED) {
     const int n = c.rows * c.stride;
@@ -796,6 +811,28 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
   Env<NL> v;
   load_env(c, s, e, v, ENV != ENV_SIMPLE);
   int plans = s.plans[e];
+  // SEQ: the segment index, the sums over the segments so far, and the condition_on_desired values
+  // (the handle's for the first segment, then what the segment before wrote: never stored)
+  int seg = 0, len_sum = 0;
+  double ret_sum = 0.0;
+  float cond_q[NL], cond_qd[NL];
+  if constexpr (SEQ) {
+    if (c.cond_desired && (v.flags & 2u)) {
+#pragma unroll
+      for (int k = 0; k < NL; ++k) { cond_q[k] = s.cond[k * N + e]; cond_qd[k] = s.cond[(NL + k) * N + e]; }
+    }
+    // the pair's segment rows start as the padding (+0.0 / 0) and each executed segment overwrites its
+    // own.  Here, in front of the loop, and not where the pair leaves it: the compiler keeps the
+    // wave-uniform `pointer given` tests as lane masks, and one made inside the loop holds only the
+    // lanes still running, so a test read after the loop by lanes that left earlier is wrong for them
+    // (seen in the ISA: with seg_ret = NULL those lanes stored their padding through the null pointer).
+    const int64_t CN = (int64_t)seq.n_cand * N;
+    for (int g = 0; g < seq.n_seg; ++g) {
+      if (seq.seg_ret) seq.seg_ret[g * CN + prow] = 0.0;
+      if (seq.seg_len) seq.seg_len[g * CN + prow] = 0;
+    }
+  }
+next_segment:   // (SEQ only: the epilogue jumps back here; every local below starts afresh)
   const int s0 = c.replan ? v.steps : 0;       // init_time = current_traj_steps * dt if replanning
 
   // initial conditions (black_box_wrapper.py:123-127)
@@ -803,11 +840,17 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
   const bool has_cond = c.cond_desired && (v.flags & 2u);
 #pragma unroll
   for (int k = 0; k < NL; ++k) {
-    ic_q[k] = has_cond ? (double)s.cond[k * N + e] : v.q[k];
-    ic_qd[k] = has_cond ? (double)s.cond[(NL + k) * N + e] : v.qd[k];
+    if constexpr (SEQ) {
+      ic_q[k] = has_cond ? (double)cond_q[k] : v.q[k];
+      ic_qd[k] = has_cond ? (double)cond_qd[k] : v.qd[k];
+    } else {
+      ic_q[k] = has_cond ? (double)s.cond[k * N + e] : v.q[k];
+      ic_qd[k] = has_cond ? (double)s.cond[(NL + k) * N + e] : v.qd[k];
+    }
   }
   Traj<(MP == MP_GIVEN ? MP_NONE : MP), NL, NB, false, ENV == ENV_SIMPLE> tg;
-  if (MP != MP_GIVEN) tg.init(c, params + prow * c.n_params, lds_tab, s0, ic_q, ic_qd);
+  if (MP != MP_GIVEN)
+    tg.init(c, params + (SEQ ? (int64_t)seg * seq.n_cand * N + prow : prow) * c.n_params, lds_tab, s0, ic_q, ic_qd);
 
   plans += 1;
   // first sample index k with (k + 1 + s0) % replan == 0 (black_box_wrapper.py:233); the loop
@@ -1010,6 +1053,13 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
 #pragma unroll
         for (int d = 0; d < NL; ++d) { s.cond[d * N + e] = pos[d]; s.cond[(NL + d) * N + e] = vel[d]; }
         v.flags |= 2u;
+      }
+      if constexpr (SEQ) {   // the same values for the next segment, in registers
+        if (c.cond_desired) {
+#pragma unroll
+          for (int d = 0; d < NL; ++d) { cond_q[d] = pos[d]; cond_qd[d] = vel[d]; }
+          v.flags |= 2u;
+        }
       }
       return true;
     }
@@ -1282,7 +1332,11 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
   FGX_STAMP(o, e, 3);
   // the epilogue needs FK of the final q; a last sample at env step >= 199 (always a generic one)
   // has just computed it for its reward
-  if (ENV == ENV_SIMPLE && !(v.steps - 1 >= 199 && !c.sched_state)) v.fk();
+  // (SEQ: FK is a function of q alone and the next segment recomputes it where it is read -- the env
+  // step of the direct envs, fk_always under a state-dependent schedule -- so only the segment whose
+  // observation leaves the thread needs it here)
+  const bool seq_last = SEQ && (term || trunc || seg + 1 >= seq.n_seg);
+  if (ENV == ENV_SIMPLE && !(v.steps - 1 >= 199 && !c.sched_state) && (!SEQ || seq_last)) v.fk();
   const double ret = (L > 128 && rew_row) ? pairwise_strided(rew_row, N, L) : ps.result(L, split);
   FGX_STAMP(o, e, 4);
   if constexpr (PAIR) {   // the env's length once: from its even lane
@@ -1297,7 +1351,24 @@ __device__ __forceinline__ void episode_body(const DevCfg& c, const DevState& s,
       }
     }
   }
-  if constexpr (ROLL) {
+  if constexpr (SEQ) {
+    // the segment's row, the sums (returns: ((r_0 + r_1) + r_2) + ..., as fgx_rollout_raw), then either
+    // the pair's outputs (the rows of the segments it does not run hold the padding already), or the
+    // next segment
+    const int64_t CN = (int64_t)seq.n_cand * N;
+    if (seq.seg_ret) seq.seg_ret[seg * CN + prow] = ret;
+    if (seq.seg_len) seq.seg_len[seg * CN + prow] = L;
+    ret_sum = (seg == 0) ? ret : ret_sum + ret;
+    len_sum += L;
+    ++seg;
+    if (!seq_last) goto next_segment;
+    o.ret[prow] = ret_sum;
+    o.term[prow] = term;
+    o.trunc[prow] = trunc;
+    o.tlen[prow] = len_sum;
+    seq.segments[prow] = seg;
+    if (o.obs) emit_obs(c, v, c.return_context, o.obs + prow * c.out_dim, nullptr, false, true);
+  } else if constexpr (ROLL) {
     // episode_epilogue's outputs without auto-reset, on the candidate row; no state leaves the thread
     o.ret[prow] = ret;
     o.term[prow] = term;
@@ -1409,6 +1480,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 template <int ENV, int MP, int CTRL, int NL, int NB>
 __global__ __launch_bounds__(256) void k_rollout_bb(DevCfg c, DevState s, const float* __restrict__ params, Outputs o) {
   episode_body<ENV, MP, CTRL, NL, NB, false, false, false, true>(c, s, params, nullptr, nullptr, o);
+}
+
+// k_rollout_seq: up to n_seg successive black-box steps of C candidate parameter sequences per env,
+// params [S][C][N][n_params], the handle left as it is (fgx_rollout_bb_seq, include/fgx.h; the reference:
+// successive BlackBoxWrapper.step calls on copies of the env, black_box_wrapper.py:170-253, until the
+// first terminated | truncated).  k_rollout_bb's layout and body with the segment loop (episode_body
+// SEQ): the env, `plans` and the condition_on_desired values stay in registers between segments, the
+// step rewards of a long segment are read back at its end, so the one [C][T][N] workspace serves all.
+// The new pointers are arguments of this kernel alone: Outputs / DevCfg / DevState keep their layout.
+template <int ENV, int MP, int CTRL, int NL, int NB>
+__global__ __launch_bounds__(256) void k_rollout_seq(DevCfg c, DevState s, const float* __restrict__ params, Outputs o,
+                                                     int n_seg, int n_cand, int32_t* segments, double* seg_ret,
+                                                     int32_t* seg_len) {
+  SeqArgs seq;
+  seq.n_seg = n_seg;
+  seq.n_cand = n_cand;
+  seq.segments = segments;
+  seq.seg_ret = seg_ret;
+  seq.seg_len = seg_len;
+  episode_body<ENV, MP, CTRL, NL, NB, false, false, false, true, true>(c, s, params, nullptr, nullptr, o, seq);
 }
 
 // info_level 2, SimpleReacher: the per-step observation components that need trigonometry -- cos /

@@ -75,6 +75,10 @@ struct NlOps {
   // (fgx_rollout_bb, include/fgx.h); s.rew: the caller's workspace, o: the candidate-row outputs
   int (*rollout_bb)(const DevCfg& c, const DevState& s, const float* params, int n_cand, const Outputs& o,
                     hipStream_t stream, std::string& err);
+  // k_rollout_seq: up to n_seg successive black-box steps of n_cand parameter sequences per env
+  // (fgx_rollout_bb_seq, include/fgx.h); s.rew and o as for rollout_bb, o.tlen / o.ret: the sums
+  int (*rollout_seq)(const DevCfg& c, const DevState& s, const float* params, int n_seg, int n_cand, const Outputs& o,
+                     int32_t* segments, double* seg_ret, int32_t* seg_len, hipStream_t stream, std::string& err);
 };
 }  // namespace fgx
 const fgx::NlOps* fgx_nl_ops_1();

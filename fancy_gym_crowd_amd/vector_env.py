@@ -52,6 +52,8 @@ class Box:
 
 
 Rollout = collections.namedtuple("Rollout", "returns lengths terminated truncated observations rewards")
+SequenceRollout = collections.namedtuple(
+    "SequenceRollout", "returns lengths segments terminated truncated observations segment_returns segment_lengths")
 
 
 def _ptr(t):
@@ -372,6 +374,59 @@ class BlackBoxVectorEnv:
         if agg == "mean":
             ret = torch.where(length > 0, ret / length.to(torch.float64), ret)
         return ret, length, te, tr, obs
+
+    def rollout_sequence(self, params, *, observations=True, segment_returns=True):
+        """What would happen from here over the next S black-box steps (plan segments): C candidate
+        parameter sequences per env from every env's current state in one launch
+        (fgx_rollout_bb_seq), with the envs left untouched.  params: [S, C, N, n_params], or
+        [S, N, n_params] for one candidate (the outputs then have no C axis).  Segment s of a pair is
+        bit for bit the s-th of successive step(params[s, c]) calls on a copy of the env with
+        autoreset off; the pair stops after its first terminated | truncated segment, so M <= S
+        segments run (M = 1 on an id without replanning) and the rows of later segments are never
+        read.  Returns a SequenceRollout: returns [C, N] f64 (the segment returns added left to
+        right), lengths [C, N] i32 (sum of the segment lengths), segments [C, N] i32 (M),
+        terminated / truncated [C, N] bool and observations [C, N, out_dim] f32 of segment M - 1 (None
+        unless `observations`), segment_returns [S, C, N] f64 and segment_lengths [S, C, N] i32 (+0.0
+        and 0 from segment M on; None unless `segment_returns`).  reward_aggregation must be sum or
+        mean (mean: every segment's return is its sum / length), as for rollout()."""
+        _order_check(self)
+        agg = self.meta["reward_aggregation"]
+        if agg not in ("sum", "mean"):
+            raise ValueError("rollout_sequence() serves reward_aggregation np.sum / np.mean only: the others read "
+                             "the per-step rewards, which rollout_sequence() does not return")
+        a = torch.as_tensor(params, device=self.device)
+        N = self.num_envs
+        if a.dim() not in (3, 4) or tuple(a.shape[-2:]) != (N, self.n_params):
+            raise ValueError(f"params must have shape [S, C, {N}, {self.n_params}] or [S, {N}, {self.n_params}], "
+                             f"not {list(a.shape)}")
+        S = int(a.shape[0])
+        C = int(a.shape[1]) if a.dim() == 4 else 1
+        if S < 1 or C < 1:
+            raise ValueError("params: the segment count S (first axis) and the candidate count C must be >= 1")
+        a = a.to(torch.float32).contiguous()
+        ws, nbytes = self._rollout_workspace(C)
+        batch = (C, N) if a.dim() == 4 else (N,)
+        dev = self.device
+        ret = torch.empty(batch, dtype=torch.float64, device=dev)
+        length = torch.empty(batch, dtype=torch.int32, device=dev)
+        segs = torch.empty(batch, dtype=torch.int32, device=dev)
+        te = torch.empty(batch, dtype=torch.bool, device=dev)
+        tr = torch.empty(batch, dtype=torch.bool, device=dev)
+        obs = torch.empty(batch + (self.out_dim,), dtype=torch.float32, device=dev) if observations else None
+        rows = segment_returns or agg == "mean"   # (the mean is taken per segment, from the rows)
+        sret = torch.empty((S,) + batch, dtype=torch.float64, device=dev) if rows else None
+        slen = torch.empty((S,) + batch, dtype=torch.int32, device=dev) if rows else None
+        _lib.check(self._eng.lib.fgx_rollout_bb_seq(self._eng.h, _ptr(a), S, C, _ptr(ret), _ptr(length), _ptr(segs),
+                                                    _ptr(te), _ptr(tr), _ptr(obs), _ptr(sret), _ptr(slen), _ptr(ws),
+                                                    nbytes, self._eng.stream()))
+        if agg == "mean":
+            sret = torch.where(slen > 0, sret / slen.to(torch.float64), sret)
+            ret = sret[0]
+            for g in range(1, S):   # left to right over the executed segments, on the device
+                ret = torch.where(segs > g, ret + sret[g], ret)
+        if not segment_returns:
+            sret = slen = None
+        return SequenceRollout(ret, length, segs, te, tr, obs, sret, slen)
 
     def _rollout_workspace(self, C):
         """The cached device workspace of rollout() for C candidates (fgx_rollout_bb_workspace: the

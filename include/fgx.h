@@ -24,6 +24,8 @@
  *                     sequences per env, from its current state
  *   fgx_rollout_bb    BlackBoxWrapper.step(action) called on copies of the  black_box/black_box_wrapper.py:170-253
  *                     env, once per candidate parameter vector
+ *   fgx_rollout_bb_seq  the same called S times in succession on each copy, black_box/black_box_wrapper.py:170-253
+ *                     until the episode ends (one call per plan segment)
  *   fgx_get_state /   env.unwrapped.current_pos/current_vel, goal, hole black_box/raw_interface_wrapper.py:24-44
  *   fgx_set_state     (test access; five of the eleven state arrays)
  *   fgx_snapshot /    the complete state of every env: bit-exact resume        (no counterpart: deepcopy /
@@ -317,6 +319,38 @@ int fgx_rollout_bb_workspace(void* handle, int32_t n_cand, int64_t* bytes);
 int fgx_rollout_bb(void* handle, const float* params, int32_t n_cand, double* returns,
                    int32_t* lengths, uint8_t* terminated, uint8_t* truncated, float* obs,
                    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Black-box sequence rollouts: up to n_seg successive black-box steps (plan segments) of n_cand
+ * parameter sequences per env from the env's current state, in one launch (k_rollout_seq: one thread
+ * per (env, candidate), the env in registers between segments), with nothing of the handle changed.
+ * On a replanning id one black-box step is one plan segment, and the task reward arrives at the end of
+ * the episode: this is the look-ahead that sees it.  For env e, candidate c and segment s = 0, 1, ...
+ * segment s applies params[s, c, e, :] and is bit for bit what the s-th of successive
+ *   fgx_step(handle', params[s, c], ..., final_obs = NULL, info = NULL, autoreset = 0)
+ * calls gives on a copy handle' of the handle in its current state: plan start row and initial
+ * conditions, condition_on_desired (the values written at the end of segment s are the ones segment
+ * s + 1 reads), plans against max_planning_times counted up across the segments, the static and
+ * state-dependent replanning clauses, TimeLimit, controller and clip, the HoleReacher reward state,
+ * the segment's return in numpy's pairwise order, time-aware column and context mask.  A sequence
+ * stops after the first segment whose terminated | truncated is set, or after segment n_seg - 1:
+ * M in [1, n_seg] segments are executed (always 1 on an id without replanning).
+ *   params       f32 [n_seg, n_cand, N, n_params]  rows of segments >= M are never read
+ *   returns      f64 [n_cand, N]            ((r_0 + r_1) + r_2) + ...: left-to-right f64 adds from r_0
+ *   lengths      i32 [n_cand, N]            sum of the segments' trajectory_length
+ *   segments     i32 [n_cand, N]            M
+ *   terminated, truncated  u8 [n_cand, N]   flags of segment M - 1
+ *   obs          f32 [n_cand, N, out_obs_dim]      observation after segment M - 1 (NULL ok)
+ *   seg_returns  f64 [n_seg, n_cand, N]     segment return for s < M, +0.0 for s >= M (NULL ok)
+ *   seg_lengths  i32 [n_seg, n_cand, N]     trajectory_length of segment s, 0 for s >= M (NULL ok)
+ *   workspace    fgx_rollout_bb_workspace(handle, n_cand) bytes, as for fgx_rollout_bb: a segment's step
+ *                rewards are read back at that segment's end, so one [C][T][N] buffer serves all.
+ * Handle state, refusals and launch properties are fgx_rollout_bb's; FGX_E_INVALID also for
+ * n_seg < 1. */
+int fgx_rollout_bb_seq(void* handle, const float* params, int32_t n_seg, int32_t n_cand,
+                       double* returns, int32_t* lengths, int32_t* segments,
+                       uint8_t* terminated, uint8_t* truncated, float* obs,
+                       double* seg_returns, int32_t* seg_lengths,
+                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* State access (tests / checkpoint): q, qd [N, dof] f64, goal [N, 2] f64, hole [N, 3] f64
  * (HoleReacher: x, width, depth; ViaPointReacher: via x, via y, 0), steps [N] i32.

@@ -427,8 +427,104 @@ def rollout_bb(env_id, N, C, rounds=4, reps=5):
           flush=True)
 
 
+def rollout_seq(env_id, N, C=16, S=8, rounds=4, reps=5, scale=1.0):
+    """S plan segments of C candidate sequences per env at N envs from a fresh reset, on the id with
+    ReplanEvery(25), alternated `rounds` times in one session.  (a) the route without
+    fgx_rollout_bb_seq: the fgx_copy_envs fan-out of the N envs into a handle of N * C envs and S
+    fgx_step(autoreset = 0) calls there, captured in one HIP graph; (b) one fgx_rollout_bb_seq launch.
+    HIP events around `reps` replays / launches.  Asserts that (b)'s returns, lengths and segment counts
+    equal (a)'s bit for bit on the segments (a) runs before a pair's end ((a) steps every pair S times).
+    scale: of the N(0, 1) parameters (HoleReacher at 10: plans that collide, pairs ending at different segments)."""
+    import ctypes
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    over = {"black_box_kwargs": {"replanning_schedule": fgx.ReplanEvery(25)}}
+    mk = lambda n: fgx.make(env_id, num_envs=n, device=dev, info_level=0, autoreset=False, mp_config_override=over)   # noqa: E731
+    env, big = mk(N), mk(N * C)
+    env.reset(seed=0)
+    big.reset(seed=0)
+    lib = env._eng.lib
+    M = N * C
+    params = torch.from_numpy(np.random.default_rng(1234).standard_normal((S, C, N, env.n_params), dtype=np.float32)
+                              * np.float32(scale)).to(dev)
+    src = torch.arange(N, device=dev).repeat(C)
+    dst = torch.arange(M, device=dev)
+    e = lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device=dev)   # noqa: E731
+    a_ret, a_ln, a_te, a_tr = e(S, M, dt=torch.float64), e(S, M, dt=torch.int32), e(S, M, dt=torch.uint8), e(S, M, dt=torch.uint8)
+    a_obs = e(M, env.out_dim)
+    ret, ln, sg = e(C, N, dt=torch.float64), e(C, N, dt=torch.int32), e(C, N, dt=torch.int32)
+    te, tr, obs = e(C, N, dt=torch.uint8), e(C, N, dt=torch.uint8), e(C, N, env.out_dim)
+    sret, sln = e(S, C, N, dt=torch.float64), e(S, C, N, dt=torch.int32)
+    nws = ctypes.c_int64()
+    assert lib.fgx_rollout_bb_workspace(env._eng.h, C, ctypes.byref(nws)) == 0, lib.fgx_last_error()
+    ws = torch.empty(nws.value // 8, dtype=torch.float64, device=dev) if nws.value else None
+
+    def route_a():
+        assert lib.fgx_copy_envs(big._eng.h, env._eng.h, p(dst), p(src), M, env._eng.stream()) == 0, lib.fgx_last_error()
+        for s in range(S):
+            assert lib.fgx_step(big._eng.h, p(params[s]), p(a_obs), p(a_ret[s]), p(a_te[s]), p(a_tr[s]), p(a_ln[s]), None,
+                                None, 0, env._eng.stream()) == 0, lib.fgx_last_error()
+
+    def roll():
+        return lib.fgx_rollout_bb_seq(env._eng.h, p(params), S, C, p(ret), p(ln), p(sg), p(te), p(tr), p(obs), p(sret),
+                                      p(sln), p(ws), nws.value, env._eng.stream())
+
+    route_a()
+    assert roll() == 0, lib.fgx_last_error()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        route_a()
+    torch.cuda.synchronize()
+
+    def many(fn):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3   # us per call
+
+    forms = {"a: copy + S steps on N*C envs (one graph)": lambda: many(g.replay), "b: fgx_rollout_bb_seq": lambda: many(roll)}
+    times = {k: [] for k in forms}
+    for _ in range(rounds):
+        for k, fn in forms.items():
+            times[k].append(fn())
+    # the same episodes: (a)'s rows until each pair's first done, summed left to right
+    g.replay()
+    assert roll() == 0
+    torch.cuda.synchronize()
+    run = torch.ones(M, dtype=torch.bool, device=dev)
+    w_ret, w_ln, w_sg = a_ret[0].clone(), torch.zeros(M, dtype=torch.int32, device=dev), torch.zeros(M, dtype=torch.int32, device=dev)
+    for s in range(S):
+        if s:
+            w_ret = torch.where(run, w_ret + a_ret[s], w_ret)
+        w_ln = torch.where(run, w_ln + a_ln[s], w_ln)
+        w_sg = torch.where(run, w_sg + 1, w_sg)
+        run = run & ~((a_te[s] | a_tr[s]) != 0)
+    same = bool(torch.equal(ret.reshape(-1).view(torch.int64), w_ret.view(torch.int64)) and
+                torch.equal(ln.reshape(-1), w_ln) and torch.equal(sg.reshape(-1), w_sg))
+    assert same, "fgx_rollout_bb_seq differs from the copy + step route"
+    build = lib.fgx_build_id().decode()
+    med = lambda v: (sorted(v)[(len(v) - 1) // 2] + sorted(v)[len(v) // 2]) / 2   # noqa: E731
+    hist = torch.bincount(sg.reshape(-1), minlength=S + 1)[1:].tolist()
+    for k, v in times.items():
+        print(json.dumps(dict(mode="rollout_seq", form=k, config=env_id, schedule="ReplanEvery(25)", param_scale=scale, envs=N, n_cand=C,
+                              n_seg=S, pairs=M, step_kernel=big.episode_kernel(), us_median=med(v), us_min=min(v),
+                              us_max=max(v), rounds=rounds, same_bits_as_step=same, segments_hist=hist,
+                              workspace_bytes=nws.value, build=build)), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["episode", "traj", "raw"]
+    if "rollout_seq" in which:   # C = 16 sequences of S = 8 segments per env: copy + S steps against one launch
+        for env_id, ns in (("fancy_ProDMP/SimpleReacher-v0", (8192, 65536)), ("fancy_ProDMP/HoleReacher-v0", (4096, 65536))):
+            for n in ns:
+                rollout_seq(env_id, n)
+                torch.cuda.empty_cache()
+        rollout_seq("fancy_ProDMP/HoleReacher-v0", 65536, scale=10.0)   # ragged ends
     if "rollout_bb" in which:   # C = 16 candidates per env: the copy + step route against fgx_rollout_bb
         for env_id in ("fancy_ProMP/LongSimpleReacher-v0", "fancy_ProDMP/HoleReacher-v0"):
             for n in (65536, 4096):
